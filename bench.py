@@ -12,9 +12,11 @@ N GPUs: one process per GPU (torchrun, RCCL).  Items are sharded row-wise (stron
 1M x 1M), the user side is replicated, and each step ends with ONE all-gather of the per-shard top-10 lists followed
 by the local merge (tensorrec_amd/sharding.py).
 
-Extra objects on the JSON line: "roofline" (K2, MFMA-bound; K1's HBM roofline is under "roofline_k1"),
-"cpu_baseline" (the oracle's NumPy/torch-CPU path on the host cores, on a bounded user tile), "parity" (a live check of
-a sample of users against the oracle inside this run).
+A plain run sets up, warms up, times --steps steps and prints the line; "roofline" (K2, MFMA-bound; K1's HBM roofline is
+under "roofline_k1") comes from the HIP events of those same steps.  --dump-outputs DIR writes the top-k lists of the last
+timed step as .npy files (dump_outputs).  Everything that takes work of its own runs only with --full: "cpu_baseline" (the
+oracle's NumPy/torch-CPU path on the host cores, on a bounded user tile), "parity" (a live check of a sample of users against
+the oracle inside this run), the fit leg, the other precisions and configurations, the public-API call and the extra rooflines.
 """
 import argparse
 import json
@@ -34,6 +36,8 @@ FP32_MFMA_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
 FIT_SHARD_USERS = 49152             # the oracle's large fit shard: 4.9M sampled pairs (>= 2^22: the binned route), ~30 s of CPU per step
 GATHER_CEILING_512MB_GBS = 7420.0    # measured: bare 512-byte row gathers from a 512 MB table (profiles/r05_gather_ceiling_512.jsonl)
+DUMP_MAX_USERS = 1 << 18            # --dump-outputs: users written at most (k = 10: 10 + 21 + 2 MB)
+DUMP_SAMPLE_SEED = 0
 
 
 def parse():
@@ -78,7 +82,17 @@ def parse():
                          "one line -- no workload (runs without a GPU under TREC_DIST_BACKEND=gloo: tests/test_host_logic.py)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=INT",
                     help="diagnostic: set a kernel tuning knob (trec_set_tuning), e.g. blockmax_pipelined=0")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every record beyond the headline figure: oracle parity, fit leg, CPU baselines, fp32 / bf16 "
+                         "modes, public API, extra rooflines, the other configurations (the --no-* switches and --configs "
+                         "narrow this set); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the top-k values and item ids of the last timed step to DIR/*.npy (all users, or a fixed "
+                         "seeded sample of %d users when there are more)" % DUMP_MAX_USERS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def csrc_stamp():
@@ -132,6 +146,24 @@ def attach_traffic(roof, file_glob, kernel_prefix, sources, note=""):
     roof["traffic_note"] = "(2*FETCH_SIZE + WRITE_SIZE) KB per launch from %s%s" % (name, note)
     if "TCC_HIT" in vals and "TCC_MISS" in vals:
         roof["l2_hit_rate"] = vals["TCC_HIT"] / (vals["TCC_HIT"] + vals["TCC_MISS"])
+
+
+def dump_outputs(out_dir, vals, idx, max_users=DUMP_MAX_USERS, seed=DUMP_SAMPLE_SEED):
+    """--dump-outputs: what the timed step hands its caller -- the per-user top-k values [U, k] (fp32) and item ids [U, k] --
+    as out_dir/topk_values.npy (float32) and out_dir/topk_ids.npy (float64, exact), and the rows they are of as
+    out_dir/user_ids.npy (float64).  All users when there are at most `max_users`, else a fixed seeded sample of that many
+    (the same users in every run with the same arguments)."""
+    import torch
+    n = int(vals.shape[0])
+    if n <= max_users:
+        users = np.arange(n, dtype=np.int64)
+    else:
+        users = np.sort(np.random.default_rng(seed).choice(n, size=max_users, replace=False))
+    sel = torch.from_numpy(users).to(vals.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "topk_values.npy"), vals[sel].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "topk_ids.npy"), idx[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "user_ids.npy"), users.astype(np.float64))
 
 
 def cpu_baseline(n_items, d, k, n_users_sample, seed=0):
@@ -542,13 +574,15 @@ def main():
     elapsed = sharding.max_over_ranks(elapsed, device)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = float(U) * float(I) / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[0], out[1])     # (rank 0's users: all of them for N = 1)
 
-    if exact and prefilter == "int8":
+    if args.full and exact and prefilter == "int8":
         ops.CANDIDATE_STATS = True                   # one untimed step with the list statistics on (a reduction + a host read)
         out = step()
         ops.CANDIDATE_STATS = False
         torch.cuda.synchronize()
-    if world > 1:
+    if args.full and world > 1:
         # parity sample needs every rank's item rows: one untimed all-gather (shards are padded to equal length)
         vals, idx, user_repr, item_repr_local = out
         per = -(-I // world)
@@ -562,7 +596,7 @@ def main():
             padb[: n_local] = ops.sparse_matvec(f_i, beta_i).reshape(-1)
         item_bias_full = sharding.all_gather_cat(padb, dim=0)[:I].contiguous()
     fit = None
-    if not args.no_fit:
+    if args.full and not args.no_fit:
         try:                      # every rank takes part (data-parallel over users for world > 1)
             del ws
             torch.cuda.empty_cache()
@@ -637,7 +671,7 @@ def main():
     # weight table is 16x the L2 and 2x the Infinity Cache, so (unlike a small table) every gathered row is memory
     # traffic and nnz * d * 4 is an honest algorithmic byte count (checked against PMC: profiles/*k1_multi_pmc*.txt)
     roofline_k1_multi = None
-    if world == 1 and not args.no_k1_multi:
+    if args.full and world == 1 and not args.no_k1_multi:
         try:
             nnz_row, F = 20, 1_000_000
             n_rows = min(U, 1_000_000)
@@ -686,43 +720,44 @@ def main():
 
     # ---- live parity check against the oracle (checker only): the timed step's own output, on sampled users ----
     parity = None
-    try:
-        from oracle import oracle as O
-        import bench_records as BR
-        vals, idx, user_repr, item_repr = out
-        n_sample = args.parity_users if exact else 32
-        n_have = int(vals.shape[0])               # rank 0 holds all users (N = 1) or its own slice [0, n_have) (N > 1)
-        sample = np.unique(np.linspace(0, n_have - 1, min(n_sample, n_have)).astype(np.int64))
-        sample_dev = torch.from_numpy(sample).to(device)
-        got_i = idx[sample_dev].cpu().numpy()
-        got_v = vals[sample_dev].cpu().numpy()
-        if world == 1 and not args.unbiased:
-            # the oracle starts from the WEIGHTS: its own SpMM (tr_oracle.c) over the feature rows of the sampled users and of
-            # every item, its own bias projection (non-zero biases), its fp32 score chain, its top-k
-            fs = BR._identity_rows(sample, U)
-            fi = sp.identity(I, dtype=np.float32, format="csr")
-            us_all = O.spmm_exact(fs, w_u.cpu().numpy())
-            it = O.spmm_exact(fi, w_i.cpu().numpy())
-            ub_h = O.spmm_exact(fs, beta_u.cpu().numpy()).reshape(-1)
-            ib_h = O.spmm_exact(fi, beta_i.cpu().numpy()).reshape(-1)
-            source = "oracle SpMM + bias projection from the weights (non-zero biases)"
-        else:
-            # item shards: rank 0 does not hold the other ranks' weights; the gathered representations feed the oracle
-            us_all, it = user_repr[sample_dev].cpu().numpy(), item_repr.cpu().numpy()
-            ub_h = None if args.unbiased else ops.sparse_matvec(f_u, beta_u)[sample_dev].cpu().numpy()
-            ib_h = None if args.unbiased else item_bias_full.cpu().numpy()
-            source = "gathered device representations and biases"
-        parity = BR.oracle_topk_parity(O, us_all, it, ub_h, ib_h, got_v, got_i, k)
-        parity["mode"] = args.precision
-        parity["oracle_inputs"] = source
-        if exact:
-            parity["filter"] = dict(ops.LAST_FILTER_STATS)
-    except Exception as exc:      # the measurement stands on its own; report why the check could not run
-        parity = {"error": repr(exc)}
+    if args.full:
+        try:
+            from oracle import oracle as O
+            import bench_records as BR
+            vals, idx, user_repr, item_repr = out
+            n_sample = args.parity_users if exact else 32
+            n_have = int(vals.shape[0])               # rank 0 holds all users (N = 1) or its own slice [0, n_have) (N > 1)
+            sample = np.unique(np.linspace(0, n_have - 1, min(n_sample, n_have)).astype(np.int64))
+            sample_dev = torch.from_numpy(sample).to(device)
+            got_i = idx[sample_dev].cpu().numpy()
+            got_v = vals[sample_dev].cpu().numpy()
+            if world == 1 and not args.unbiased:
+                # the oracle starts from the WEIGHTS: its own SpMM (tr_oracle.c) over the feature rows of the sampled users and of
+                # every item, its own bias projection (non-zero biases), its fp32 score chain, its top-k
+                fs = BR._identity_rows(sample, U)
+                fi = sp.identity(I, dtype=np.float32, format="csr")
+                us_all = O.spmm_exact(fs, w_u.cpu().numpy())
+                it = O.spmm_exact(fi, w_i.cpu().numpy())
+                ub_h = O.spmm_exact(fs, beta_u.cpu().numpy()).reshape(-1)
+                ib_h = O.spmm_exact(fi, beta_i.cpu().numpy()).reshape(-1)
+                source = "oracle SpMM + bias projection from the weights (non-zero biases)"
+            else:
+                # item shards: rank 0 does not hold the other ranks' weights; the gathered representations feed the oracle
+                us_all, it = user_repr[sample_dev].cpu().numpy(), item_repr.cpu().numpy()
+                ub_h = None if args.unbiased else ops.sparse_matvec(f_u, beta_u)[sample_dev].cpu().numpy()
+                ib_h = None if args.unbiased else item_bias_full.cpu().numpy()
+                source = "gathered device representations and biases"
+            parity = BR.oracle_topk_parity(O, us_all, it, ub_h, ib_h, got_v, got_i, k)
+            parity["mode"] = args.precision
+            parity["oracle_inputs"] = source
+            if exact:
+                parity["filter"] = dict(ops.LAST_FILTER_STATS)
+        except Exception as exc:      # the measurement stands on its own; report why the check could not run
+            parity = {"error": repr(exc)}
 
     # ---- the all-fp32-MFMA form of the same top-k (v_mfma_f32_32x32x2_f32 throughout), as a driver-run record ----
     fp32_mode = None
-    if exact and world == 1 and not args.no_fp32_mode:
+    if args.full and exact and world == 1 and not args.no_fp32_mode:
         try:
             vals, idx, user_repr, item_repr = out
             n32 = min(U, 65536)
@@ -760,7 +795,7 @@ def main():
     # ---- the bf16-filter form of the same exact top-k (no int8 stage): north_star's bf16 MFMA score kernel, dense, as a
     # driver-run record beside the cascade that is timed above ----
     bf16_mode = None
-    if cascade and world == 1 and not args.no_fp32_mode:
+    if args.full and cascade and world == 1 and not args.no_fp32_mode:
         try:
             vals, idx, user_repr, item_repr = out
             ub2 = None if args.unbiased else ops.sparse_matvec(f_u, beta_u)
@@ -810,7 +845,7 @@ def main():
     # and recognised by content afterwards; representations, user-side preparation, cascade; lists returned on the device), with
     # its default user batch -- the documented drop-in call next to the ops-level step that is timed above
     public_api = None
-    if exact and world == 1 and not args.no_fp32_mode:
+    if args.full and exact and world == 1 and not args.no_fp32_mode:
         try:
             vals, idx, user_repr, item_repr = out
             model = T.TensorRec(n_components=d, biased=not args.unbiased, seed=0)
@@ -851,7 +886,7 @@ def main():
     # ---- further driver-visible records (rank 0, one GPU): fitted weights, fit parity, multi-nnz parity, the other configs
     trained = parity_fit = parity_fit_binned = parity_multi = configs = None
     oracle_small_shard_s = oracle_shard_s = None
-    if world == 1 and args.configs == "all" and exact:
+    if args.full and world == 1 and args.configs == "all" and exact:
         import bench_records as BR
         try:
             trained = BR.trained_weights_record(make_step, device, U, I, d, k, steps=max(2, min(args.steps, 3)),
@@ -881,7 +916,7 @@ def main():
         configs = BR.config_records(device)
 
     cpu = cpu_fit = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(I, d, k, args.cpu_users)
         if fit is not None and "error" not in fit:
             try:
@@ -924,24 +959,25 @@ def main():
     # kernel at its per-rank size, the shared floor / the exchange plan real, nothing on the wire) -- read from the committed
     # profiles of the same code; the multi-GPU numbers themselves are the driver's to measure
     scale_emulation = None
-    try:
-        import glob
-        rs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_rank_sim_n8.json")))
-        fs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_fit_rank_sim_n8.json")))
-        scale_emulation = {"note": "one-GPU emulations of ONE rank of an 8-GPU run (committed profiles, not measured in this run)"}
-        if rs:
-            r_ = json.load(open(rs[-1]))
-            scale_emulation["predict"] = {"file": os.path.basename(rs[-1]), "per_rank_step_ms": r_.get("per_rank_step_ms_at_N8_emulated"),
-                                          "ideal_ms": ms_per_step / 8.0 if world == 1 else None,
-                                          "kernels_ms": r_.get("kernels_ms"),
-                                          "exchange_bytes_received_per_rank": r_.get("exchange_bytes_received_per_rank")}
-        if fs:
-            f_ = json.load(open(fs[-1]))
-            scale_emulation["fit"] = {"file": os.path.basename(fs[-1]), "per_rank_compute_ms_per_step": f_.get("per_rank_compute_ms_per_step"),
-                                      "plan": f_.get("plan"), "wire_bytes_per_rank_and_step": f_.get("wire_bytes_per_rank_and_step_total"),
-                                      "round3_wire_bytes_per_rank_and_step": f_.get("round3_wire_bytes_per_rank_and_step")}
-    except Exception as exc:
-        scale_emulation = {"error": repr(exc)}
+    if args.full:
+        try:
+            import glob
+            rs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_rank_sim_n8.json")))
+            fs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_fit_rank_sim_n8.json")))
+            scale_emulation = {"note": "one-GPU emulations of ONE rank of an 8-GPU run (committed profiles, not measured in this run)"}
+            if rs:
+                r_ = json.load(open(rs[-1]))
+                scale_emulation["predict"] = {"file": os.path.basename(rs[-1]), "per_rank_step_ms": r_.get("per_rank_step_ms_at_N8_emulated"),
+                                              "ideal_ms": ms_per_step / 8.0 if world == 1 else None,
+                                              "kernels_ms": r_.get("kernels_ms"),
+                                              "exchange_bytes_received_per_rank": r_.get("exchange_bytes_received_per_rank")}
+            if fs:
+                f_ = json.load(open(fs[-1]))
+                scale_emulation["fit"] = {"file": os.path.basename(fs[-1]), "per_rank_compute_ms_per_step": f_.get("per_rank_compute_ms_per_step"),
+                                          "plan": f_.get("plan"), "wire_bytes_per_rank_and_step": f_.get("wire_bytes_per_rank_and_step_total"),
+                                          "round3_wire_bytes_per_rank_and_step": f_.get("round3_wire_bytes_per_rank_and_step")}
+        except Exception as exc:
+            scale_emulation = {"error": repr(exc)}
     line["scale_emulation"] = scale_emulation
     # dispatches per step the way rocprofv3 counts them (kernels + fills + copies): read from the committed kernel-stats of this
     # command when one exists for the current round; the HIP-event count (our own launches only) is always present

@@ -2,7 +2,7 @@
 # A/B of two builds of the library on the headline step, same box: gpu_lib_ab.sh libA.so libB.so ...
 set +e
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; OUT=gpurun_out; mkdir -p $OUT
-ARGS="--prewarm-seconds 0 --configs headline --no-fit --no-cpu-baseline --no-k1-multi --no-fp32-mode --parity-users 64 --steps 5 --warmup 2"
+ARGS="--full --prewarm-seconds 0 --configs headline --no-fit --no-cpu-baseline --no-k1-multi --no-fp32-mode --parity-users 64 --steps 5 --warmup 2"
 for L in "$@"; do
 ( TREC_HIP_LIB=$PWD/tensorrec_amd/$L timeout 600 python bench.py $ARGS $EXTRA_TUNE > $OUT/lib_ab.json 2> $OUT/lib_ab.err )
 python - <<PY

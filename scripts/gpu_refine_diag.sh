@@ -5,7 +5,7 @@
 set +e
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; OUT=gpurun_out; mkdir -p $OUT
 export TREC_HIP_LIB=$PWD/tensorrec_amd/libtensorrec_hip_diag.so
-ARGS="--prewarm-seconds 0 --configs headline --no-fit --no-cpu-baseline --no-k1-multi --no-fp32-mode --parity-users 64 --steps 5 --warmup 2"
+ARGS="--full --prewarm-seconds 0 --configs headline --no-fit --no-cpu-baseline --no-k1-multi --no-fp32-mode --parity-users 64 --steps 5 --warmup 2"
 for V in "$@"; do
 ( timeout 600 python scripts/refine_diag.py $ARGS --tune cascade_cand_diag=$V $EXTRA_TUNE > $OUT/refine_diag_$V.json 2> $OUT/refine_diag_$V.err )
 grep refine_workgroups $OUT/refine_diag_$V.err > $OUT/refine_diag_clk_$V.json

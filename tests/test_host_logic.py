@@ -219,6 +219,39 @@ def test_bench_cpu_baseline_leg_and_defaults(monkeypatch):
     assert a.steps >= 1 and a.warmup >= 0
 
 
+def test_bench_full_and_dump_options(monkeypatch, tmp_path):
+    """bench.py: --full is off by default (a plain run times the headline step only), --steps must be at least 1, and
+    dump_outputs writes the lists of the last step as float32 values, float64 ids and the float64 rows they belong to --
+    every row when they fit, else the same seeded sample of DUMP_MAX_USERS rows in every call."""
+    import sys
+    import torch
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path), "--steps", "3"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path) and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+    rng = np.random.default_rng(0)
+    vals = torch.from_numpy(np.sort(rng.standard_normal((50, 4)).astype(np.float32), axis=1)[:, ::-1].copy())
+    idx = torch.from_numpy(rng.integers(0, 1 << 20, size=(50, 4), dtype=np.int32))
+    bench.dump_outputs(str(tmp_path / "all"), vals, idx)
+    v, i, u = (np.load(str(tmp_path / "all" / n)) for n in ("topk_values.npy", "topk_ids.npy", "user_ids.npy"))
+    assert v.dtype == np.float32 and i.dtype == np.float64 and u.dtype == np.float64
+    assert np.array_equal(v, vals.numpy()) and np.array_equal(i, idx.numpy()) and np.array_equal(u, np.arange(50))
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), vals, idx, max_users=8)
+    u1, u2 = np.load(str(tmp_path / "s1" / "user_ids.npy")), np.load(str(tmp_path / "s2" / "user_ids.npy"))
+    assert np.array_equal(u1, u2) and u1.shape == (8,) and np.all(np.diff(u1) > 0)
+    rows = u1.astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "topk_ids.npy")), idx.numpy()[rows])
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "topk_values.npy")), vals.numpy()[rows])
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` started BARE (no torch.distributed.run around it, the driver's multi-GPU command): the process
     becomes the launcher of two ranks of the same command; rank 0 alone prints the line.  --launch-check stops each rank after
