@@ -757,6 +757,28 @@ int trec_adam_tf_step_dev(float* w, float* m, float* v, const float* grad, int64
 int trec_sample_items_dev(int64_t n_users, int64_t user_base, int32_t n_items, int32_t n_sampled, int32_t replace,
                           uint64_t seed, const uint32_t* step_dev, int32_t* out, void* stream);
 
+/* ---- EXTENSION: exclusions (csrc/exclude.hip, docs/exclusion.md; no TF counterpart) -------------------------------
+ * Each user's excluded ("seen") items as one CSR: ex_ptr int64 [n_rows + 1] (absolute positions), ex_idx int32 sorted and
+ * de-duplicated per row.  rows (nullable): row r of the call uses CSR row rows[r] (identity when NULL).
+ * trec_exclude_filter_topk: in_vals / in_idx [n_users, kf] = every user's EXACT top-kf (value desc, index asc, places beyond the
+ * catalogue -inf / -1) -> out [n_users, k]: the first k entries whose id is not excluded, then -inf / -1.  flag[u] = 1 (and
+ * n_flagged [1], zeroed by the caller, counts it) when fewer than k entries survived AND the kf-th place holds a real item: only
+ * then may a non-excluded item beyond the list belong to the first k.
+ * trec_topk_rows_excluded: exact top-k (1 <= k <= 1024, value desc, index asc) of every row of a score slab [n_rows, n_cols]
+ * (stride ld) with the row's excluded columns skipped; places beyond the row's non-excluded entries are -inf / -1.  The excluded
+ * cells of `scores` are OVERWRITTEN with a NaN sentinel first (ex_ptr / ex_idx NULL: no exclusions).  -0.0 ties +0.0; a
+ * genuine NaN score ranks behind -inf.
+ * trec_exclude_rank_adjust: pairs grouped by user (pair_ptr int64 [n_users + 1], t_idx / t_score their item ids and exact
+ * scores) and the users' excluded items (ex_ptr / ex_idx / ex_score, same user rows): counts[t] -= #{x in E_u : s_x > s_t or
+ * (s_x == s_t and x < t)} -- K2r's rule, so count + 1 becomes the rank among the non-excluded items.                       */
+int trec_exclude_filter_topk(const float* in_vals, const int32_t* in_idx, int32_t kf, int64_t n_users, int32_t k,
+                             const int64_t* ex_ptr, const int32_t* ex_idx, const int32_t* rows, float* out_vals,
+                             int32_t* out_idx, int32_t* flag, int32_t* n_flagged, void* stream);
+int trec_topk_rows_excluded(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols, int32_t k, const int64_t* ex_ptr,
+                            const int32_t* ex_idx, const int32_t* rows, float* out_vals, int32_t* out_idx, void* stream);
+int trec_exclude_rank_adjust(const int64_t* pair_ptr, const int32_t* t_idx, const float* t_score, const int64_t* ex_ptr,
+                             const int32_t* ex_idx, const float* ex_score, int64_t n_users, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

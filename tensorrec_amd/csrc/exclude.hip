@@ -1,0 +1,404 @@
+// tensorrec_amd/csrc/exclude.hip -- exact top-k and pair ranks with each user's "seen" items excluded (docs/exclusion.md).
+//
+// The exclusions of a call arrive as one CSR: ex_ptr int64 [n_rows + 1] (absolute positions into ex_idx), ex_idx int32 sorted
+// ascending and de-duplicated within a row.  `rows` (nullable) maps the kernel's user / slab row r to its CSR row rows[r]
+// (identity when NULL) -- the gathered users of the masked slab pass.
+//
+// 1. trec_exclude_filter_topk (tier 1).  One wave per user reads the user's EXACT top-k' list (value desc, index asc; places
+//    beyond the catalogue -inf / -1 at the end), binary-searches every id in the user's exclusion row, and compacts the survivors
+//    in order (ballot + mbcnt) into [n, k].  Correctness: the first k non-excluded entries of an exact top-k' list ARE the first k
+//    non-excluded items overall -- every item missing from the list is behind its k'-th entry, hence behind every entry of the
+//    list.  So a user with >= k survivors is exact; a user whose list ran out of catalogue (k'-th place -1) has no item outside
+//    the list and is exact with padding.  Only a user with < k survivors AND a real k'-th item may have non-excluded items
+//    beyond the list: flag[u] = 1, and the caller re-does it on the masked slab (2).
+//
+// 2. trec_topk_rows_excluded (tier 2).  The excluded cells of a score slab are overwritten with a sentinel NaN (bits 0xFFFFFFFF),
+//    then one 1,024-thread workgroup per row selects the row's exact top-k (k <= 1024) by an order-preserving uint32 key in which
+//    the sentinel is 0 (never selected), a genuine NaN is 1 (behind -inf, ties by index), -inf is 0x007FFFFF and -0.0 is +0.0.
+//    Pass 1 streams the row once: every thread keeps the largest key of its strided share, and the k-th largest of those 1,024
+//    maxima is a floor L <= the row's k-th largest key (k threads each hold an entry >= L).  Pass 2 appends the entries >= L
+//    (typically a few times k) to LDS; a bitonic sort by (key desc, index asc) orders them and the first k are written.  Rows
+//    where more than SEL_CAP entries reach L (heavy ties, few valid threads) take the exact path instead: a radix select of the
+//    k-th key (11 + 11 + 10 bits), then -- if that key is tied across the k-th place -- a radix select of the index among the
+//    tied entries, and one pass that appends exactly k entries.  Places beyond the row's non-excluded entries are -inf / -1.
+//
+// 3. trec_exclude_rank_adjust.  Pair ranks counted over every item (K2r, trec_rank_of_pairs_by_user) minus the excluded items
+//    ahead of the target, with K2r's rule: counts[t] -= #{x in E_u : s_x > s_t or (s_x == s_t and x < t)}.  One wave per user;
+//    the scores of both sides must come from the same chain as the count (trec_pair_score_exact, or the score slab itself).
+#include "topk_common.hpp"
+
+namespace {
+
+constexpr unsigned int EX_SENTINEL = 0xFFFFFFFFu;     // a negative NaN with every payload bit set: "excluded"
+constexpr int SEL_THREADS = 1024;
+constexpr int SEL_WAVES = SEL_THREADS / TREC_WAVE;
+constexpr int SEL_CAP = 4096;                        // LDS candidate slots of the floor path (32 KB)
+constexpr int SEL_BINS = 2048;
+
+__device__ __forceinline__ unsigned int lanes_below(unsigned long long mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
+}
+
+__device__ __forceinline__ bool row_contains(const int32_t* __restrict__ ex_idx, int64_t b, int64_t e, int32_t id)
+{
+    while (b < e) {
+        const int64_t m = (b + e) >> 1;
+        const int32_t x = ex_idx[m];
+        if (x == id) return true;
+        if (x < id) b = m + 1;
+        else e = m;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(256) void exclude_filter_kernel(const float* __restrict__ in_vals, const int32_t* __restrict__ in_idx,
+                                                             int kf, int64_t n_users, int k, const int64_t* __restrict__ ex_ptr,
+                                                             const int32_t* __restrict__ ex_idx, const int32_t* __restrict__ rows,
+                                                             float* __restrict__ out_vals, int32_t* __restrict__ out_idx,
+                                                             int32_t* __restrict__ flag, int32_t* __restrict__ n_flagged)
+{
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= n_users) return;
+    const int lane = lane_id();
+    const int64_t r = rows ? (int64_t)rows[u] : u;
+    const int64_t b = ex_ptr[r], e = ex_ptr[r + 1];
+    const float* iv = in_vals + u * kf;
+    const int32_t* ii = in_idx + u * kf;
+    float* ov = out_vals + u * k;
+    int32_t* oi = out_idx + u * k;
+    int kept = 0;                                                   // wave-uniform
+    for (int j0 = 0; j0 < kf && kept < k; j0 += TREC_WAVE) {
+        const int j = j0 + lane;
+        int32_t id = -1;
+        float v = -INFINITY;
+        if (j < kf) {
+            id = ii[j];
+            v = iv[j];
+        }
+        const bool keep = id >= 0 && !row_contains(ex_idx, b, e, id);
+        const unsigned long long mask = __ballot(keep);
+        const int pos = kept + (int)lanes_below(mask);
+        if (keep && pos < k) {
+            ov[pos] = v;
+            oi[pos] = id;
+        }
+        kept += __popcll(mask);
+    }
+    for (int p = kept + lane; p < k; p += TREC_WAVE) {
+        ov[p] = -INFINITY;
+        oi[p] = -1;
+    }
+    if (lane == 0) {
+        const bool redo = kept < k && ii[kf - 1] >= 0;
+        flag[u] = redo ? 1 : 0;
+        if (redo) atomicAdd(n_flagged, 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void exclude_mask_kernel(float* __restrict__ scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                                                           const int64_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
+                                                           const int32_t* __restrict__ rows)
+{
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= n_rows) return;
+    const int64_t r = rows ? (int64_t)rows[u] : u;
+    const int64_t b = ex_ptr[r], e = ex_ptr[r + 1];
+    for (int64_t p = b + lane_id(); p < e; p += TREC_WAVE) {
+        const int32_t c = ex_idx[p];
+        if (c >= 0 && c < n_cols) scores[u * ld + c] = __uint_as_float(EX_SENTINEL);
+    }
+}
+
+__device__ __forceinline__ unsigned int sel_key(float f)
+{
+    unsigned int b = __float_as_uint(f);
+    if (b == 0x80000000u) b = 0u;                                   // -0.0 == +0.0: one key
+    if ((b & 0x7fffffffu) > 0x7f800000u) return b == EX_SENTINEL ? 0u : 1u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// f(key, column) for every entry of the row; coalesced, float4 when the row is 16-byte aligned
+template <typename F>
+__device__ __forceinline__ void for_each_key(const float* __restrict__ s, int64_t n, F f)
+{
+    int64_t done = 0;
+    if ((((uintptr_t)s) & 15u) == 0) {
+        const f32x4* s4 = (const f32x4*)s;
+        const int64_t n4 = n >> 2;
+        for (int64_t q = threadIdx.x; q < n4; q += SEL_THREADS) {
+            const f32x4 x = s4[q];
+            f(sel_key(x[0]), 4 * q);
+            f(sel_key(x[1]), 4 * q + 1);
+            f(sel_key(x[2]), 4 * q + 2);
+            f(sel_key(x[3]), 4 * q + 3);
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + threadIdx.x; i < n; i += SEL_THREADS) f(sel_key(s[i]), i);
+}
+
+// exclusive / inclusive block prefix of one value per thread (thread order)
+__device__ __forceinline__ void block_scan(unsigned int x, unsigned int* wtot, unsigned int& excl, unsigned int& incl)
+{
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    unsigned int v = x;
+#pragma unroll
+    for (int o = 1; o < TREC_WAVE; o <<= 1) {
+        const unsigned int t = __shfl_up(v, o, TREC_WAVE);
+        if (lane >= o) v += t;
+    }
+    if (lane == TREC_WAVE - 1) wtot[w] = v;
+    __syncthreads();
+    unsigned int before = 0;
+    for (int i = 0; i < w; ++i) before += wtot[i];
+    __syncthreads();
+    incl = before + v;
+    excl = incl - x;
+}
+
+// the bin of a 2,048-bin histogram where the `need`-th entry lies, counting from the top bin (desc) or the bottom bin (!desc);
+// every thread returns (bin, entries in the bins before it)
+__device__ __forceinline__ void find_bin(const unsigned int* hist, unsigned int need, bool desc, unsigned int* wtot, unsigned int* s_res,
+                                         unsigned int& bin, unsigned int& before)
+{
+    const unsigned int b0 = desc ? SEL_BINS - 1 - 2 * threadIdx.x : 2 * threadIdx.x;
+    const unsigned int b1 = desc ? b0 - 1 : b0 + 1;
+    unsigned int excl, incl;
+    block_scan(hist[b0] + hist[b1], wtot, excl, incl);
+    if (excl < need && need <= incl) {
+        if (excl + hist[b0] >= need) {
+            s_res[0] = b0;
+            s_res[1] = excl;
+        } else {
+            s_res[0] = b1;
+            s_res[1] = excl + hist[b0];
+        }
+    }
+    __syncthreads();
+    bin = s_res[0];
+    before = s_res[1];
+    __syncthreads();
+}
+
+// bitonic sort of cand[0, n) descending (n a power of two, <= SEL_CAP)
+__device__ __forceinline__ void sort_desc(unsigned long long* cand, int n)
+{
+    for (int size = 2; size <= n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < (n >> 1); t += SEL_THREADS) {
+                const int i = 2 * stride * (t / stride) + (t % stride);
+                const int j = i + stride;
+                const bool desc = (i & size) == 0;
+                const unsigned long long a = cand[i], b = cand[j];
+                if ((a < b) == desc) {
+                    cand[i] = b;
+                    cand[j] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long cand_key(unsigned int key, int64_t col)
+{
+    return ((unsigned long long)key << 32) | (unsigned int)(~(unsigned int)col);
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void topk_rows_excluded_kernel(const float* __restrict__ scores, int64_t ld, int64_t n_cols,
+                                                                         int k, float* __restrict__ out_vals,
+                                                                         int32_t* __restrict__ out_idx)
+{
+    __shared__ unsigned long long cand[SEL_CAP];
+    __shared__ unsigned int hist[SEL_BINS];
+    __shared__ unsigned int wtot[SEL_WAVES];
+    __shared__ unsigned int s_res[2];
+    __shared__ unsigned int s_cnt;
+    const int64_t row = blockIdx.x;
+    const float* s = scores + row * ld;
+    const int lane = lane_id();
+
+    // pass 1: per-thread maximum key and the number of non-excluded entries
+    unsigned int tmax = 0, nvalid = 0;
+    for_each_key(s, n_cols, [&](unsigned int key, int64_t) {
+        tmax = key > tmax ? key : tmax;
+        nvalid += key != 0u;
+    });
+    unsigned int ex, valid;
+    block_scan(nvalid, wtot, ex, valid);
+    if (threadIdx.x == SEL_THREADS - 1) s_res[0] = valid;
+    __syncthreads();
+    valid = s_res[0];
+    const int m = (int)(valid < (unsigned int)k ? valid : (unsigned int)k);      // places that hold an item
+    cand[threadIdx.x] = (unsigned long long)tmax << 32;
+    __syncthreads();
+    sort_desc(cand, SEL_THREADS);
+    unsigned int floor_key = m > 0 ? (unsigned int)(cand[m - 1] >> 32) : 1u;
+    if (floor_key == 0u || (unsigned int)m < (unsigned int)k) floor_key = 1u;   // (fewer than k valid: every valid entry)
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+
+    // pass 2: the entries reaching the floor
+    for_each_key(s, n_cols, [&](unsigned int key, int64_t col) {
+        const bool take = key >= floor_key;
+        const unsigned long long mask = __ballot(take);
+        if (mask == 0ull) return;
+        unsigned int base = 0;
+        if (lane == __builtin_ctzll(mask)) base = atomicAdd(&s_cnt, (unsigned int)__popcll(mask));
+        base = __shfl(base, __builtin_ctzll(mask), TREC_WAVE);
+        const unsigned int pos = base + lanes_below(mask);
+        if (take && pos < SEL_CAP) cand[pos] = cand_key(key, col);
+    });
+    __syncthreads();
+    unsigned int c = s_cnt;
+    __syncthreads();
+
+    if (c > SEL_CAP) {
+        // exact path: radix select of the m-th largest key among keys >= floor_key
+        unsigned int prefix = 0, himask = 0, need = (unsigned int)m, eq = 0;
+        const int shifts[3] = {21, 10, 0};
+        const unsigned int dmasks[3] = {0x7ffu, 0x7ffu, 0x3ffu};
+        for (int d = 0; d < 3; ++d) {
+            for (int i = threadIdx.x; i < SEL_BINS; i += SEL_THREADS) hist[i] = 0;
+            __syncthreads();
+            const int sh = shifts[d];
+            for_each_key(s, n_cols, [&](unsigned int key, int64_t) {
+                if (key >= floor_key && (key & himask) == prefix) atomicAdd(&hist[(key >> sh) & dmasks[d]], 1u);
+            });
+            __syncthreads();
+            unsigned int bin, before;
+            find_bin(hist, need, true, wtot, s_res, bin, before);
+            need -= before;
+            eq = hist[bin];
+            prefix |= bin << sh;
+            himask |= dmasks[d] << sh;
+            __syncthreads();
+        }
+        const unsigned int T = prefix;
+        // the kth key is tied beyond the m-th place: the need-th smallest column among the entries equal to T
+        unsigned int last_col = 0xffffffffu;
+        if (eq > need) {
+            unsigned int cpre = 0, cmask = 0, cneed = need;
+            const int cshifts[3] = {21, 10, 0};
+            const unsigned int cmasks[3] = {0x7ffu, 0x7ffu, 0x3ffu};
+            for (int d = 0; d < 3; ++d) {
+                for (int i = threadIdx.x; i < SEL_BINS; i += SEL_THREADS) hist[i] = 0;
+                __syncthreads();
+                const int sh = cshifts[d];
+                for_each_key(s, n_cols, [&](unsigned int key, int64_t col) {
+                    const unsigned int cc = (unsigned int)col;
+                    if (key == T && (cc & cmask) == cpre) atomicAdd(&hist[(cc >> sh) & cmasks[d]], 1u);
+                });
+                __syncthreads();
+                unsigned int bin, before;
+                find_bin(hist, cneed, false, wtot, s_res, bin, before);
+                cneed -= before;
+                cpre |= bin << sh;
+                cmask |= cmasks[d] << sh;
+                __syncthreads();
+            }
+            last_col = cpre;
+        }
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        for_each_key(s, n_cols, [&](unsigned int key, int64_t col) {
+            const bool take = key > T || (key == T && (unsigned int)col <= last_col);
+            const unsigned long long mask = __ballot(take);
+            if (mask == 0ull) return;
+            unsigned int base = 0;
+            if (lane == __builtin_ctzll(mask)) base = atomicAdd(&s_cnt, (unsigned int)__popcll(mask));
+            base = __shfl(base, __builtin_ctzll(mask), TREC_WAVE);
+            const unsigned int pos = base + lanes_below(mask);
+            if (take && pos < (unsigned int)k) cand[pos] = cand_key(key, col);
+        });
+        __syncthreads();
+        c = s_cnt < (unsigned int)m ? s_cnt : (unsigned int)m;             // (== m by construction)
+        __syncthreads();
+    }
+
+    // sort the c candidates (value desc, column asc) and write the first k places
+    int n2 = 1;
+    while (n2 < (int)c) n2 <<= 1;
+    for (int i = (int)c + threadIdx.x; i < n2; i += SEL_THREADS) cand[i] = 0ull;
+    __syncthreads();
+    if (n2 > 1) sort_desc(cand, n2);
+    float* ov = out_vals + row * k;
+    int32_t* oi = out_idx + row * k;
+    for (int p = threadIdx.x; p < k; p += SEL_THREADS) {
+        if (p < m && p < (int)c) {
+            const unsigned int col = ~(unsigned int)cand[p];
+            ov[p] = s[col];
+            oi[p] = (int32_t)col;
+        } else {
+            ov[p] = -INFINITY;
+            oi[p] = -1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void exclude_rank_adjust_kernel(const int64_t* __restrict__ pair_ptr, const int32_t* __restrict__ t_idx,
+                                                                  const float* __restrict__ t_score, const int64_t* __restrict__ ex_ptr,
+                                                                  const int32_t* __restrict__ ex_idx, const float* __restrict__ ex_score,
+                                                                  int64_t n_users, int32_t* __restrict__ counts)
+{
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= n_users) return;
+    const int64_t p0 = pair_ptr[u], p1 = pair_ptr[u + 1], e0 = ex_ptr[u], e1 = ex_ptr[u + 1];
+    if (p0 == p1 || e0 == e1) return;
+    for (int64_t p = p0 + lane_id(); p < p1; p += TREC_WAVE) {
+        const int32_t t = t_idx[p];
+        const float st = t_score[p];
+        int32_t ahead = 0;
+        for (int64_t x = e0; x < e1; ++x) {
+            const float sx = ex_score[x];
+            ahead += (sx > st || (sx == st && ex_idx[x] < t)) ? 1 : 0;
+        }
+        counts[p] -= ahead;
+    }
+}
+
+}  // namespace
+
+extern "C" int trec_exclude_filter_topk(const float* in_vals, const int32_t* in_idx, int32_t kf, int64_t n_users, int32_t k,
+                                        const int64_t* ex_ptr, const int32_t* ex_idx, const int32_t* rows, float* out_vals,
+                                        int32_t* out_idx, int32_t* flag, int32_t* n_flagged, void* stream)
+{
+    TREC_REQUIRE(in_vals && in_idx && ex_ptr && ex_idx && out_vals && out_idx && flag && n_flagged,
+                 "trec_exclude_filter_topk: null pointer");
+    TREC_REQUIRE(k >= 1 && kf >= k, "trec_exclude_filter_topk: need 1 <= k <= kf");
+    if (n_users == 0) return TREC_OK;
+    hipLaunchKernelGGL(exclude_filter_kernel, dim3((unsigned)ceil_div64(n_users, 4)), dim3(256), 0, (hipStream_t)stream, in_vals, in_idx,
+                       kf, n_users, k, ex_ptr, ex_idx, rows, out_vals, out_idx, flag, n_flagged);
+    return trec_check_launch("trec_exclude_filter_topk");
+}
+
+extern "C" int trec_topk_rows_excluded(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols, int32_t k, const int64_t* ex_ptr,
+                                       const int32_t* ex_idx, const int32_t* rows, float* out_vals, int32_t* out_idx, void* stream)
+{
+    TREC_REQUIRE(scores && out_vals && out_idx, "trec_topk_rows_excluded: null pointer");
+    TREC_REQUIRE((ex_ptr == nullptr) == (ex_idx == nullptr), "trec_topk_rows_excluded: ex_ptr and ex_idx go together");
+    TREC_REQUIRE(k >= 1 && k <= SEL_THREADS, "trec_topk_rows_excluded: need 1 <= k <= 1024");
+    TREC_REQUIRE(n_cols >= 0 && n_cols <= 0x7fffffffLL && ld >= n_cols, "trec_topk_rows_excluded: bad row length / stride");
+    TREC_REQUIRE(n_rows <= 0x7fffffffLL, "trec_topk_rows_excluded: too many rows");
+    if (n_rows == 0) return TREC_OK;
+    if (ex_ptr) {
+        hipLaunchKernelGGL(exclude_mask_kernel, dim3((unsigned)ceil_div64(n_rows, 4)), dim3(256), 0, (hipStream_t)stream, scores, ld,
+                           n_rows, n_cols, ex_ptr, ex_idx, rows);
+        const int rc = trec_check_launch("trec_topk_rows_excluded (mask)");
+        if (rc != TREC_OK) return rc;
+    }
+    hipLaunchKernelGGL(topk_rows_excluded_kernel, dim3((unsigned)n_rows), dim3(SEL_THREADS), 0, (hipStream_t)stream, scores, ld, n_cols, k,
+                       out_vals, out_idx);
+    return trec_check_launch("trec_topk_rows_excluded");
+}
+
+extern "C" int trec_exclude_rank_adjust(const int64_t* pair_ptr, const int32_t* t_idx, const float* t_score, const int64_t* ex_ptr,
+                                        const int32_t* ex_idx, const float* ex_score, int64_t n_users, int32_t* counts, void* stream)
+{
+    TREC_REQUIRE(pair_ptr && t_idx && t_score && ex_ptr && ex_idx && ex_score && counts, "trec_exclude_rank_adjust: null pointer");
+    if (n_users == 0) return TREC_OK;
+    hipLaunchKernelGGL(exclude_rank_adjust_kernel, dim3((unsigned)ceil_div64(n_users, 4)), dim3(256), 0, (hipStream_t)stream, pair_ptr,
+                       t_idx, t_score, ex_ptr, ex_idx, ex_score, n_users, counts);
+    return trec_check_launch("trec_exclude_rank_adjust");
+}

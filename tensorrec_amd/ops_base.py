@@ -1273,3 +1273,14 @@ def sample_items_dev(n_users, n_items, n_sampled, replace, seed, state, device="
     N.call("trec_sample_items_dev", n_users, int(user_base), n_items, n_sampled, 1 if replace else 0,
            int(seed) & (2 ** 64 - 1), step_ptr, N.ptr(out))
     return out
+
+
+def exclude_rank_adjust(pair_ptr, t_idx, t_score, ex_ptr, ex_idx, ex_score, counts):
+    """Pair rank counts over every item -> counts over the non-excluded items, in place (csrc/exclude.hip): for each target t of
+    user u, minus #{x in E_u : s_x > s_t or (s_x == s_t and x < t)}.  ``pair_ptr`` / ``ex_ptr``: device int64 [n_users + 1] over the
+    same user rows (absolute positions into t_* / ex_*); scores from the same chain as the counts."""
+    n_users = int(pair_ptr.numel()) - 1
+    with _timed("exclude_rank_adjust"):
+        N.call("trec_exclude_rank_adjust", N.ptr(pair_ptr), N.ptr(t_idx), N.ptr(t_score), N.ptr(ex_ptr), N.ptr(ex_idx),
+               N.ptr(ex_score), n_users, N.ptr(counts))
+    return counts

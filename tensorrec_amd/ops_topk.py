@@ -1605,3 +1605,40 @@ def topk_merge(cand_vals, cand_idx, k):
     oi = torch.empty((n_u, k), dtype=torch.int32, device=cand_vals.device)
     N.call("trec_topk_merge", N.ptr(cand_vals), N.ptr(cand_idx), n_u, n_cand, k, N.ptr(ov), N.ptr(oi))
     return ov, oi
+
+
+EXCLUDE_K_MAX = 1024      # largest k of topk_rows_excluded (one 1,024-thread workgroup per row)
+
+
+def exclude_filter_topk(vals, idx, k, ex_ptr, ex_idx, rows=None):
+    """Tier 1 of predict_top_k(exclude=...) (csrc/exclude.hip): every user's exact top-k' lists [n, k'] -> the first k
+    non-excluded entries [n, k] (-inf / -1 beyond them), flag int32 [n] (1: fewer than k survived and the list did not run out of
+    catalogue -- the user must be re-done on the masked slab) and the number of flagged users (device int32 [1]).  ``ex_ptr``:
+    device int64 CSR row pointers whose row u (or ``rows[u]``) belongs to list row u; ``ex_idx``: device int32 sorted columns."""
+    vals, idx = vals.contiguous(), idx.contiguous()
+    n, kf = idx.shape
+    dev = idx.device
+    ov = torch.empty((n, int(k)), dtype=torch.float32, device=dev)
+    oi = torch.empty((n, int(k)), dtype=torch.int32, device=dev)
+    flag = torch.empty((n,), dtype=torch.int32, device=dev)
+    n_flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with _timed("exclude_filter_topk"):
+        N.call("trec_exclude_filter_topk", N.ptr(vals), N.ptr(idx), int(kf), n, int(k), N.ptr(ex_ptr), N.ptr(ex_idx), N.ptr(rows),
+               N.ptr(ov), N.ptr(oi), N.ptr(flag), N.ptr(n_flag))
+    return ov, oi, flag, n_flag
+
+
+def topk_rows_excluded(scores, k, ex_ptr=None, ex_idx=None, rows=None):
+    """Exact top-k (k <= 1024) of every row of a score slab with the row's excluded columns skipped: (values [n, k], ids int32
+    [n, k]) in rank_predictions' order, -inf / -1 beyond the row's non-excluded entries (csrc/exclude.hip).  The excluded cells
+    of ``scores`` are OVERWRITTEN (a NaN sentinel).  ``ex_ptr`` / ``ex_idx``: as exclude_filter_topk (None: nothing excluded)."""
+    if not 1 <= int(k) <= EXCLUDE_K_MAX:
+        raise ValueError("topk_rows_excluded supports 1 <= k <= %d (got %r)" % (EXCLUDE_K_MAX, k))
+    scores = _f32c(scores)
+    n, n_i = scores.shape
+    vals = torch.empty((n, int(k)), dtype=torch.float32, device=scores.device)
+    idx = torch.empty((n, int(k)), dtype=torch.int32, device=scores.device)
+    with _timed("topk_rows_excluded"):
+        N.call("trec_topk_rows_excluded", N.ptr(scores), scores.stride(0), n, n_i, int(k), N.ptr(ex_ptr), N.ptr(ex_idx), N.ptr(rows),
+               N.ptr(vals), N.ptr(idx))
+    return vals, idx

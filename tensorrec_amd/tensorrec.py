@@ -26,6 +26,7 @@ import torch
 from scipy import sparse as sp
 
 from . import ops
+from . import exclusion as _excl
 from . import _native as N
 from .errors import (
     ModelNotBiasedException, ModelNotFitException, ModelWithoutAttentionException, BatchNonSparseInputException
@@ -1069,13 +1070,19 @@ class TensorRec(object):
         return _to_host(rank_predictions(pred))
 
     @_on_model_device
-    def predict_rank_of_interactions(self, user_features, item_features, interactions, user_batch_size=None):
+    def predict_rank_of_interactions(self, user_features, item_features, interactions, user_batch_size=None, exclude=None):
         """EXTENSION: the ranks ``predict_rank`` would give, but only at the positive entries of ``interactions`` --
         all the evaluation metrics need (eval.py multiplies the [n_users, n_items] rank matrix by the positive mask).
         Users are walked in tiles: a [tile, n_items] score slab stays on the device and K4 ranks each positive pair
         against its row (``trec_rank_of_pairs``, or the row-sorting ``trec_rank_rows`` when users have many positives),
         so neither scores nor ranks of the full matrix ever reach the host.  Returns ``eval.PairRanks`` (accepted by every metric in place of the matrix);
-        the ranks are bit-identical to ``predict_rank(...)[rows, cols]``."""
+        the ranks are bit-identical to ``predict_rank(...)[rows, cols]``.
+
+        ``exclude`` (scipy sparse, the convention of predict_top_k's): the "filtered" protocol -- a pair's rank counts only the
+        items not excluded for its user, 1 + #{j not in E_u : s_j > s_t or (s_j == s_t and j < t)}, so every metric of eval.py on
+        the result is the filtered metric.  A positive pair that is also excluded raises ValueError.  The count over all items
+        is corrected by the excluded items ahead of the target (trec_exclude_rank_adjust), whose scores come from the chain the
+        count used: the fused path's exact pair chain, or the score slab."""
         from .eval import PairRanks
         self._check_fit('predict_rank_of_interactions')
         uf, itf = self._inference(user_features, item_features)
@@ -1093,6 +1100,16 @@ class TensorRec(object):
         if user_batch_size is None:
             user_batch_size = max(64, min(n_users, (1 << 29) // max(1, n_items)))       # <= 2 GB of fp32 scores
         device = self._store.device
+        ex = None
+        if exclude is not None:
+            ex_indptr, ex_indices = _excl.exclusion_csr(exclude, n_users, n_items)
+            if len(ex_indices) > 0:
+                n_both = _excl.overlap_count(ex_indptr, ex_indices, rows, cols)
+                if n_both:
+                    raise ValueError("%d test interaction(s) are also in exclude: a test item cannot be excluded from its own "
+                                     "ranking" % n_both)
+                ex_rows = np.repeat(np.arange(n_users, dtype=np.int32), np.diff(ex_indptr))
+                ex = (ex_indptr, ex_indices, ex_rows)
         ranks = np.zeros(len(rows), np.int32)
         bounds = np.searchsorted(rows, np.arange(0, n_users + user_batch_size, user_batch_size))
         # one taste, built-in prediction graph, fp32: no slab at all -- the count is the epilogue of the fp32 MFMA score
@@ -1111,11 +1128,27 @@ class TensorRec(object):
                 if want_sq and u_op.shape[1] != kpad:          # (score_prep returns the representation itself when d == kpad)
                     raise RuntimeError("score_prep returned an unpadded operand")
                 pair_indptr = np.searchsorted(rows, np.arange(n_users + 1)).astype(np.int64)
-                counts = ops.rank_counts_fused(u_op, i_op, kpad, user_reprs[0].shape[1], pair_indptr,
-                                               torch.from_numpy(np.ascontiguousarray(cols)).to(device),
-                                               user_bias.contiguous() if self.biased else None,
-                                               item_bias.contiguous() if self.biased else None, graph.engine_mode,
-                                               u_sq, i_sq)
+                if ex is None:
+                    counts = ops.rank_counts_fused(u_op, i_op, kpad, user_reprs[0].shape[1], pair_indptr,
+                                                   torch.from_numpy(np.ascontiguousarray(cols)).to(device),
+                                                   user_bias.contiguous() if self.biased else None,
+                                                   item_bias.contiguous() if self.biased else None, graph.engine_mode,
+                                                   u_sq, i_sq)
+                else:
+                    # the excluded items' scores and the targets' from the chain K2r compares with (trec_pair_score_exact)
+                    d = user_reprs[0].shape[1]
+                    ubc = user_bias.contiguous() if self.biased else None
+                    ibc = item_bias.contiguous() if self.biased else None
+                    xi_d = torch.from_numpy(np.ascontiguousarray(cols)).to(device)
+                    tgt = ops.pair_scores_exact(u_op, i_op, kpad, d, torch.from_numpy(rows).to(device), xi_d, ubc, ibc,
+                                                graph.engine_mode, u_sq, i_sq)
+                    counts = ops.rank_counts_fused(u_op, i_op, kpad, d, pair_indptr, xi_d, ubc, ibc, graph.engine_mode, u_sq, i_sq,
+                                                   target_scores=tgt)
+                    ex_idx_d = torch.from_numpy(ex[1]).to(device)
+                    ex_score = ops.pair_scores_exact(u_op, i_op, kpad, d, torch.from_numpy(ex[2]).to(device), ex_idx_d, ubc, ibc,
+                                                     graph.engine_mode, u_sq, i_sq)
+                    ops.exclude_rank_adjust(torch.from_numpy(pair_indptr).to(device), xi_d, tgt,
+                                            torch.from_numpy(ex[0]).to(device), ex_idx_d, ex_score, counts)
                 return PairRanks(rows, (counts + 1).cpu().numpy(), vals, n_users)
             for b, s in enumerate(range(0, n_users, user_batch_size)):
                 p0, p1 = bounds[b], bounds[b + 1]
@@ -1142,12 +1175,23 @@ class TensorRec(object):
                     target = slab[xu, xi].contiguous()
                     tile_ptr = torch.from_numpy(np.searchsorted(rows[p0:p1], np.arange(s, e + 1)).astype(np.int64)).to(device)
                     r = ops.rank_of_pairs_by_user(slab, 0, 0, n_items, tile_ptr, xi32, target, add_one=True)
+                if ex is not None and ex[0][e] > ex[0][s]:
+                    # minus the tile's excluded items ahead of each target, their scores read off the same slab
+                    q0, q1 = int(ex[0][s]), int(ex[0][e])
+                    ex_i = torch.from_numpy(ex[1][q0:q1]).to(device)
+                    ex_u = (torch.from_numpy(ex[2][q0:q1]).to(device) - s).long()
+                    ex_score = slab[ex_u, ex_i.long()].contiguous()
+                    target = slab[xu, xi].contiguous()
+                    tile_ptr = torch.from_numpy(np.searchsorted(rows[p0:p1], np.arange(s, e + 1)).astype(np.int64)).to(device)
+                    r = r.contiguous()
+                    ops.exclude_rank_adjust(tile_ptr, xi32, target, torch.from_numpy(ex[0][s:e + 1] - q0).to(device), ex_i,
+                                            ex_score, r)          # (both pointer arrays count from this tile's first entry)
                 ranks[p0:p1] = r.cpu().numpy()
         return PairRanks(rows, ranks, vals, n_users)
 
     @_on_model_device
     def predict_top_k(self, user_features, item_features, k=10, user_batch_size=None, return_device=False,
-                      item_sharded=False, item_offset=0, return_route=False):
+                      item_sharded=False, item_offset=0, return_route=False, exclude=None):
         """EXTENSION: the k best items per user -- (scores [n_users, k] float32, item ids [n_users, k] int32),
         ordered like the first k ranks of ``predict_rank`` -- computed by the fused MFMA score + top-k kernel without
         materialising [n_users, n_items] (which is 4 TB at 1M x 1M).  ``user_batch_size`` None (default): as many users per
@@ -1166,7 +1210,18 @@ class TensorRec(object):
         euclid_certified | wide_cascade | two_stage | direct | slab (attention models, k > 16 off the wide routes), "k", "sharded",
         "user_batch_size", "n_items") and, with
         ``return_route=True``, returned as a third value -- a silently slower route is the likeliest regression of this method
-        (tests/test_gpu_routes.py pins the route of every BASELINE.json configuration)."""
+        (tests/test_gpu_routes.py pins the route of every BASELINE.json configuration).
+
+        ``exclude`` (scipy sparse, at most [n_users, n_items]; missing rows / columns exclude nothing): every stored entry != 0
+        -- negative interactions included, explicit zeros not -- is left out of that user's list.  The result is the first k
+        places of ``predict_rank``'s order after the excluded items are removed, padded with (-inf, -1) when fewer than k items
+        remain; bit-identical to that definition (on bf16 models: on the bf16 scores the route uses).  The route ``k`` selects
+        runs with k' = min(that route's largest k, k + the batch's most exclusions), a kernel drops the excluded ids from the
+        exact lists, and the users left with fewer than k whose list did not run out of catalogue are re-done on masked score
+        slabs; the slab route masks its slabs directly (docs/exclusion.md).  ``last_route`` then holds "exclude": {"k_fetch",
+        "n_excluded", "n_fallback"}.  None, or a matrix without a non-zero entry: exactly the call without it.  Not with
+        ``item_sharded`` / ``item_offset`` (a follow-up: filter after the replicated merge, tier 2 per shard) and not beyond
+        k = 1,024 (ValueError)."""
         from . import sharding
         self._check_fit('predict_top_k')
         if int(k) < 1:
@@ -1175,6 +1230,17 @@ class TensorRec(object):
             raise ValueError("predict_top_k needs a built-in prediction graph")
         graph = self.prediction_graph_factory
         uf, itf = self._inference(user_features, item_features)
+        ex = None
+        if exclude is not None:
+            ex_indptr, ex_indices = _excl.exclusion_csr(exclude, uf.shape[0], itf.shape[0])
+            if len(ex_indices) > 0:
+                if bool(item_sharded) or int(item_offset) != 0:
+                    raise ValueError("predict_top_k(exclude=...) does not support item shards (item_sharded / item_offset)")
+                if int(k) > ops.EXCLUDE_K_MAX:
+                    raise ValueError("predict_top_k(exclude=...) supports k <= %d (got %d)" % (ops.EXCLUDE_K_MAX, int(k)))
+                dev = self._store.device
+                ex = {"indptr": ex_indptr, "ptr": torch.from_numpy(ex_indptr).to(dev),
+                      "idx": torch.from_numpy(ex_indices).to(dev), "k_fetch": int(k), "n_fallback": 0}
         dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
         want_sq = graph.engine_mode == ops.MODE_EUCLIDEAN
         # attention models: the softmax-weighted sum over tastes (recommendation_graphs.py:98-107) does not decompose into
@@ -1231,15 +1297,6 @@ class TensorRec(object):
         # which (superblock, user) pairs the bf16 stage has to look at at all (csrc/topk_cascade.hip)
         prefilter = ops.cascade_prefilter_for(self.n_components, n_items_min * (dist.get_world_size(self.process_group) if sharded else 1)) \
             if filtered else None
-        if user_batch_size is None:
-            route = "wide" if (wide or (euclid_filtered and k > ops.EUCLID_CANDIDATES - 4)) else \
-                ("cascade" if (filtered or euclid_filtered) else "two_stage")
-            user_batch_size = ops.topk_user_batch(uf.shape[0], itf.shape[0], self.n_components, self._store.device,
-                                                  route=route, k=k)
-            if sharded:                  # every rank walks the SAME user batches (each batch holds collectives): the smallest wins
-                ubs = torch.tensor([user_batch_size], dtype=torch.int64, device=self._store.device)
-                dist.all_reduce(ubs, op=dist.ReduceOp.MIN, group=self.process_group)
-                user_batch_size = int(ubs.item())
         if slab_route:
             route_name = "slab"
         elif euclid_filtered:
@@ -1250,9 +1307,26 @@ class TensorRec(object):
             route_name = "wide_cascade"
         else:
             route_name = method if method != "auto" else ("two_stage" if itf.shape[0] >= ops.TWO_STAGE_MIN_ITEMS else "direct")
+        # exclusions: the lists are asked for k' places (the same route's largest k at most)
+        k_all = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], 0, uf.shape[0]))
+        if user_batch_size is None:
+            route = "wide" if (wide or (euclid_filtered and k > ops.EUCLID_CANDIDATES - 4)) else \
+                ("cascade" if (filtered or euclid_filtered) else "two_stage")
+            user_batch_size = ops.topk_user_batch(uf.shape[0], itf.shape[0], self.n_components, self._store.device,
+                                                  route=route, k=k_all)
+            if sharded:                  # every rank walks the SAME user batches (each batch holds collectives): the smallest wins
+                ubs = torch.tensor([user_batch_size], dtype=torch.int64, device=self._store.device)
+                dist.all_reduce(ubs, op=dist.ReduceOp.MIN, group=self.process_group)
+                user_batch_size = int(ubs.item())
         self.last_route = {"route": route_name, "k": int(k), "sharded": bool(sharded), "n_items": int(itf.shape[0]),
                            "user_batch_size": int(user_batch_size), "precision": self.precision}
-        _ret = (lambda v_, i_: (v_, i_, dict(self.last_route))) if return_route else (lambda v_, i_: (v_, i_))
+        if ex is not None:
+            self.last_route["exclude"] = {"k_fetch": int(k), "n_excluded": int(len(ex_indices)), "n_fallback": 0}
+
+        def _ret(v_, i_):
+            if ex is not None:
+                self.last_route["exclude"].update(k_fetch=ex["k_fetch"], n_fallback=ex["n_fallback"])
+            return (v_, i_, dict(self.last_route)) if return_route else (v_, i_)
         vals, idx = [], []
         if slab_route:
             # (also: representations wider than the fused kernels' resident operand -- K-looped fp32 GEMM slabs)
@@ -1273,7 +1347,10 @@ class TensorRec(object):
                         slab = self._dense_multi([u[s:e] for u in user_reprs], attn, item_repr, ub, item_bias)
                     else:
                         slab = self._dense_prediction(user_reprs[0][s:e], item_repr, ub, item_bias)
-                    v, i = ops.topk_from_scores(slab.contiguous(), k)
+                    if ex is not None:       # (the slab route needs no over-fetch: its slabs are masked directly)
+                        v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"][s:], ex["idx"])
+                    else:
+                        v, i = ops.topk_from_scores(slab.contiguous(), k)
                     i = torch.where(i >= 0, i + int(item_offset), i)
                     if sharded:
                         if sharding.a2a_available(v, self.process_group):
@@ -1285,7 +1362,7 @@ class TensorRec(object):
             vals, idx = torch.cat(vals), torch.cat(idx)
             return _ret(vals, idx) if return_device else _ret(_to_host(vals), _to_host(idx))
         with torch.no_grad(), variable_scope(self._store):
-            user_reprs, _, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
+            user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
             ib = item_bias.contiguous() if self.biased else None
             if filtered or wide:
                 i_f = ops.score_prep_filter(item_repr, normalize=graph.engine_normalize, bias=ib, want_gstats=True)
@@ -1295,8 +1372,9 @@ class TensorRec(object):
             while s < uf.shape[0]:
                 e = min(s + user_batch_size, uf.shape[0])
                 retry = False
+                k_b = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], s, e))
                 try:
-                    v, i = self._topk_user_batch(s, e, user_reprs, item_repr, user_bias, ib, k, graph, dtype, want_sq, filtered,
+                    v, i = self._topk_user_batch(s, e, user_reprs, item_repr, user_bias, ib, k_b, graph, dtype, want_sq, filtered,
                                                  euclid_filtered, prefilter, sharded, method, floor_exchange, stats_exchange,
                                                  item_offset, i_f if (filtered or wide) else None,
                                                  None if (filtered or wide) else (i_op, i_sq, kpad), wide=wide)
@@ -1312,6 +1390,9 @@ class TensorRec(object):
                     torch.cuda.empty_cache()
                     user_batch_size = max(4096, min(user_batch_size, e - s) // 2)
                     continue
+                if ex is not None:
+                    v, i = self._exclude_batch(s, e, v, i, k, ex, user_reprs, attn_reprs, item_repr, user_bias, item_bias)
+                    ex["k_fetch"] = max(ex["k_fetch"], k_b)
                 vals.append(v)
                 idx.append(i)
                 s = e
@@ -1320,6 +1401,41 @@ class TensorRec(object):
         if return_device:
             return _ret(vals, idx)
         return _ret(_to_host(vals), _to_host(idx))
+
+    def _exclude_batch(self, s, e, v, i, k, ex, user_reprs, attn_reprs, item_repr, user_bias, item_bias):
+        """Users [s, e) of predict_top_k(exclude=...): their exact top-k' lists -> the first k non-excluded entries (tier 1), and
+        the users that kernel flags re-done on masked score slabs (tier 2) -- docs/exclusion.md."""
+        v, i, flag, n_flag = ops.exclude_filter_topk(v, i, k, ex["ptr"][s:], ex["idx"])
+        n_bad = int(n_flag.item())
+        if n_bad == 0:
+            return v, i
+        ex["n_fallback"] += n_bad
+        local = torch.nonzero(flag, as_tuple=True)[0]
+        users = local + s
+        v2, i2 = self._topk_excluded_slabs(users, user_reprs, attn_reprs, item_repr, user_bias, item_bias, k, ex)
+        v[local], i[local] = v2, i2
+        return v, i
+
+    def _topk_excluded_slabs(self, users, user_reprs, attn_reprs, item_repr, user_bias, item_bias, k, ex):
+        """Exact top-k of the given users (device int64 ids) with their excluded items skipped: score slabs of the slab route's
+        code (_dense_prediction / _dense_multi, same dtype) and the masked selection of csrc/exclude.hip."""
+        n_i = item_repr.shape[0]
+        planes = 1 + (2 * self.n_tastes if attn_reprs is not None else (self.n_tastes if self._multi() else 0))
+        step = max(1, (1 << 28) // max(1, n_i * planes))
+        rows32 = users.to(torch.int32)
+        vals, idx = [], []
+        for s in range(0, users.numel(), step):
+            sel = users[s:s + step]
+            ub = user_bias[sel] if user_bias is not None else None
+            if self._multi():
+                attn = [a[sel] for a in attn_reprs] if attn_reprs is not None else None
+                slab = self._dense_multi([u[sel] for u in user_reprs], attn, item_repr, ub, item_bias)
+            else:
+                slab = self._dense_prediction(user_reprs[0][sel], item_repr, ub, item_bias)
+            v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"], ex["idx"], rows=rows32[s:s + step].contiguous())
+            vals.append(v)
+            idx.append(i)
+        return torch.cat(vals), torch.cat(idx)
 
     def _topk_user_batch(self, s, e, user_reprs, item_repr, user_bias, ib, k, graph, dtype, want_sq, filtered, euclid_filtered,
                          prefilter, sharded, method, floor_exchange, stats_exchange, item_offset, i_f, i_ops, wide=False):
