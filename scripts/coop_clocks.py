@@ -24,7 +24,7 @@ TT._CoopStep.run = run
 model.fit_partial(inter, uf, itf, epochs=20, learning_rate=lr, n_sampled_items=S)
 torch.cuda.synchronize()
 ws = holder["ws"]
-off = (ws.numel() - 64 + 1) & ~1
+off = ws.numel() - 16                      # (the stamps close the workspace: coop_layout in csrc/step_coop.hip)
 clk = ws[off:off + 16].view(torch.int64).cpu().numpy()
 names = ["phase 1 (item tower fwd, clears)", "barrier", "phase 2 (users)", "barrier", "phase 3 (G^T U)", "barrier", "phase 4 (item tower bwd + Adam)"]
 print("step form", model.last_step_form)

@@ -150,8 +150,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
 // error <= 2^-17), the dropped Al.Bl term is <= 2^-16 of a product -- ~1.5e-5 relative per product before the sum averages it out,
 // against the 1e-4 bar of the gradients these products are (tensorrec.py:487-489).  Three MFMAs of 32 cycles do what eight fp32 MFMAs
 // of 64 cycles do: the GEMMs on the dense coefficient matrix of BASELINE configs[4] (G^T.U, G.V: 1.9 TFLOP each, 0.6-0.7 of the
-// 157 TF fp32 peak = 17-20 ms) become bound by the 14.8 GB read of G instead.  NOT used where a product is compared with the
-// oracle's fmaf chain (the ReLU layer keeps trec_gemm_f32).
+// 157 TF fp32 peak = 17-20 ms) become bound by the 14.8 GB read of G instead.  The error is relative to the PRODUCT, so a caller that
+// subtracts two large products must make them small first: the Euclidean gradients take the rows about their mean item row
+// (ops_base.wmrb_tiled_step) -- a common offset of 100x the rows' spread took the uncentred form to ~1e-3 of the largest gradient.
+// Those gradients are compared with the oracle at 1e-4; forward values that must equal the oracle's fmaf chain never come from
+// here (the ReLU layer keeps trec_gemm_f32).
 // 128 x 128 x 64 tiles (64 KB of loads in flight per workgroup: with 32-wide slabs the kernel waited for memory, 8-10 ms per GEMM
 // where reading G takes 2.5); waves 0-1 stage A, waves 2-3 stage B: a thread owns eight (row, 8 consecutive k) octets, splits them and
 // writes hi / lo as one 16-byte LDS store each ([row][k] bf16, 128-byte rows, octets XOR-swizzled); an operand whose ROW dimension is contiguous

@@ -287,9 +287,33 @@ int64_t coop_lds_bytes(int32_t n_sampled, int32_t max_pos, int32_t d, int64_t n_
 
 }  // namespace
 
+// Float offsets of the workspace arrays.  Layout: V [n_items, d] | ib | G [n_users, ldg] | dU [n_users, d] | dub | dV [n_items, d] |
+// dib | clocks [16] -- ib, dub and dib padded to multiples of 4 floats (f32x4 stores; phase 1 clears dV and the padded dib as one
+// range), the clock stamps (tuning coop_clocks: eight 8-byte wall_clock64 values) behind the padded end of dib.  The size function
+// and the pointer walk both read it, so the two cannot disagree.
+struct CoopLayout {
+    int64_t V, ib, G, dU, dub, dV, dib, clk, total;
+};
+
+inline CoopLayout coop_layout(int64_t n_users, int64_t n_items, int32_t d)
+{
+    const int64_t ni4 = (n_items + 3) / 4 * 4, nu4 = (n_users + 3) / 4 * 4;          // (ni4 is also ldg, G's row stride)
+    CoopLayout l;
+    l.V = 0;
+    l.ib = l.V + n_items * d;
+    l.G = l.ib + ni4;
+    l.dU = l.G + n_users * ni4;
+    l.dub = l.dU + n_users * d;
+    l.dV = l.dub + nu4;
+    l.dib = l.dV + n_items * d;
+    l.clk = l.dib + ni4;                     // (a multiple of 4: 8-byte aligned whenever the workspace is)
+    l.total = l.clk + 16;
+    return l;
+}
+
 // Workspace floats of trec_fit_step_coop, or -1 when the model is not covered: d % 4 == 0, d <= 128, the LDS of its phases within
-// 64 KB (n_sampled + longest interaction row in the low thousands; n_users <= ~4,000), ldg = n_items rounded up to 4.
-// Layout: V [n_items, d] | ib [n_items] | G [n_users, ldg] | dU [n_users, d] | dub [n_users] | dV [n_items, d] | dib [n_items]
+// 64 KB (n_sampled + longest interaction row in the low thousands; n_users <= ~4,000), ldg = n_items rounded up to 4.  Layout:
+// coop_layout.
 extern "C" int64_t trec_fit_step_coop_workspace_floats(int64_t n_users, int64_t n_items, int32_t d, int32_t n_sampled,
                                                        int32_t max_interactions_per_user)
 {
@@ -298,15 +322,16 @@ extern "C" int64_t trec_fit_step_coop_workspace_floats(int64_t n_users, int64_t 
     if (coop_lds_bytes(n_sampled, max_interactions_per_user, d, n_users) > 64 * 1024) return -1;
     const int64_t ldg = (n_items + 3) / 4 * 4;
     if (n_users * ldg > ((int64_t)1 << 26)) return -1;                 // G up to 256 MB: beyond that the multi-launch path is not launch-bound
-    return n_items * d + n_items + n_users * ldg + n_users * d + n_users + n_items * d + n_items + 64;
+    return coop_layout(n_users, n_items, d).total;
 }
 
 // One optimiser step of Linear (identity user features) + Linear (any item features) + DotProduct + WMRB / BalancedWMRB in ONE
 // cooperative launch (tensorrec.py:617-622 for this model family).  Weights and Adam slots are updated in place; loss [P+] and
 // pred_serial [nnz] are written for the caller's log.  samples: [n_users, n_sampled] int32, or NULL -- the kernel then draws what
-// trec_sample_items(n_users, user_base, n_items, n_sampled, 0, seed, step) would.  lr_t / l2: as trec_adam_tf_step (l2 applies to the
-// two weight tables, not to the biases).  bias pointers: all six or none.  Returns TREC_ERR_UNSUPPORTED when the device cannot hold
-// one workgroup per compute unit cooperatively (the caller then runs the multi-launch step).
+// trec_sample_items(n_users, user_base, n_items, n_sampled, 0, seed, step) would.  lr_t / l2: as trec_adam_tf_step (l2 applies to all
+// four variables: the reference regularises its bias variables too, tensorrec.py:313).  bias pointers: all six or none.  Returns
+// TREC_ERR_UNSUPPORTED when the device cannot hold one workgroup per compute unit cooperatively (the caller then runs the multi-launch
+// step).
 extern "C" int trec_fit_step_coop(float* Wu, float* Wu_m, float* Wu_v, float* Wi, float* Wi_m, float* Wi_v, float* bu, float* bu_m,
                                   float* bu_v, float* bi, float* bi_m, float* bi_v, const int64_t* f_indptr, const int32_t* f_indices,
                                   const float* f_values, const int64_t* ft_indptr, const int32_t* ft_rows, const int32_t* ft_perm,
@@ -333,21 +358,15 @@ extern "C" int trec_fit_step_coop(float* Wu, float* Wu_m, float* Wu_v, float* Wi
     a.bu = bu; a.bu_m = bu_m; a.bu_v = bu_v; a.bi = bi; a.bi_m = bi_m; a.bi_v = bi_v;
     a.f_indptr = f_indptr; a.f_indices = f_indices; a.f_values = f_values; a.ft_indptr = ft_indptr; a.ft_rows = ft_rows; a.ft_perm = ft_perm;
     a.indptr = indptr; a.xi = x_item; a.pos_slot = pos_slot; a.pos_weight = pos_weight; a.samples = samples;
-    float* w = workspace;
-    a.V = w; w += n_items * d;
-    a.ib = w; w += (n_items + 3) / 4 * 4;
-    a.G = w; w += n_users * ldg;
-    a.dU = w; w += n_users * d;
-    a.dub = w; w += (n_users + 3) / 4 * 4;
-    a.dV = w; w += n_items * d;
-    a.dib = w;
+    const CoopLayout l = coop_layout(n_users, n_items, d);
+    a.V = workspace + l.V; a.ib = workspace + l.ib; a.G = workspace + l.G; a.dU = workspace + l.dU; a.dub = workspace + l.dub;
+    a.dV = workspace + l.dV; a.dib = workspace + l.dib;
     a.loss = loss; a.pred_serial = pred_serial;
     a.n_users = n_users; a.n_items = n_items; a.n_item_features = n_item_features; a.ldg = ldg; a.user_base = user_base;
     a.S = n_sampled; a.d = d; a.max_rows = n_sampled + max_interactions_per_user; a.max_pos = max_interactions_per_user;
     a.sample_bits = sample_bits((int32_t)n_items);
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step = step;
-    // (the last 64 floats of the workspace are slack: eight 8-byte clock stamps fit there)
-    a.clk = trec_get_tuning("coop_clocks", 0) ? (long long*)(workspace + ((need - 64 + 1) & ~(int64_t)1)) : nullptr;
+    a.clk = trec_get_tuning("coop_clocks", 0) ? (long long*)(workspace + l.clk) : nullptr;
     a.ratio = (float)n_items / (float)n_sampled; a.lr_t = lr_t; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l2 = l2;
     const size_t lds = (size_t)coop_lds_bytes(n_sampled, max_interactions_per_user, d, n_users);
     int dev = 0, cus = 0, coop = 0;

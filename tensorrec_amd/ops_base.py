@@ -310,7 +310,8 @@ def l2_normalize_rows(x):
 
 def gemm_raw(a, b, trans_a=False, trans_b=False, split_bf16=False, a_colsum=False):
     """fp32 C = op(a) . op(b).  ``split_bf16``: both operands as two bf16 terms on bf16 MFMA (three products, fp32 accumulation:
-    ~1e-5 relative) -- for gradients held to 1e-4, never for a value the oracle's fmaf chain is compared with.  ``a_colsum`` (with
+    ~1e-5 relative to the product) -- for gradients held to 1e-4 whose products are not much larger than the gradient itself,
+    never for a value the oracle's fmaf chain is compared with.  ``a_colsum`` (with
     split_bf16 and trans_a): also returns the column sums of the stored ``a`` -- (C, colsum) -- taken while ``a`` is staged."""
     a, b = _f32c(a), _f32c(b)
     m = a.shape[1] if trans_a else a.shape[0]
@@ -911,21 +912,28 @@ def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, sample
     d_ib = None
     if dense:
         # d item_in: dot  dV[i] = sum_u G[u, i] U[u];  euclidean  dV[i] = sum c (V[i] - U[u]) = colsum(G)[i] V[i] - (G^T U)[i]
-        v_pad = v if ldg == n_items else torch.cat([v, torch.zeros((ldg - n_items, d), dtype=torch.float32, device=dev)])
         # (both GEMMs are gradients, held to 1e-4: split-bf16 operands on bf16 MFMA, bound by reading G instead of by the fp32
         # matrix pipe -- tuning dense_g_split_bf16 = 0: exact fp32 products)
         split = N.load().trec_get_tuning(b"dense_g_split_bf16", 1) != 0
+        # euclidean: both gradients are the difference of two products that grow with the rows' common offset (scores do not
+        # see it; trained or ReLU rows carry one), while the split product's error is relative to the product -- so the rows are
+        # taken about c = mean item row first: dU = rowsum(G) (U - c) - G . (V - c), dV = colsum(G) (V - c) - G^T . (U - c),
+        # the same values, with products of the size of the rows' spread (tests/test_gpu_fit_euclid.py)
+        c = v.mean(0) if euclid else None
+        vc = v - c if euclid else v
+        uc = u - c if euclid else u
+        v_pad = vc if ldg == n_items else torch.cat([vc, torch.zeros((ldg - n_items, d), dtype=torch.float32, device=dev)])
         with _timed("dense_g_gemm"):
             gv = gemm_raw(G, v_pad, split_bf16=split)          # [n_users, d]
-        d_u = val_rs.unsqueeze(1) * u - gv if euclid else gv
+        d_u = val_rs.unsqueeze(1) * uc - gv if euclid else gv
         want_cs = euclid or ib is not None
         with _timed("dense_g_gemm"):                          # (the column sums of G ride in the threads that stage it)
-            t = gemm_raw(G, u, trans_a=True, split_bf16=split, a_colsum=want_cs and split)
+            t = gemm_raw(G, uc, trans_a=True, split_bf16=split, a_colsum=want_cs and split)
             t, cs = t if (want_cs and split) else (t, None)
             t = t[:n_items]
         if want_cs:
             cs = cs[:n_items] if cs is not None else colsum(G)[:n_items]
-        d_v = cs.unsqueeze(1) * v - t if euclid else t.contiguous()
+        d_v = cs.unsqueeze(1) * vc - t if euclid else t.contiguous()
         if ib is not None and not euclid:
             d_ib = cs.contiguous()
         del G

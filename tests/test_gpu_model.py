@@ -646,14 +646,19 @@ def test_hip_graph_replay_equals_eager_steps(loss, kw, batch):
             assert np.allclose(wa[k], wb[k], rtol=1e-3, atol=2e-3), k
 
 
-@pytest.mark.parametrize("loss,biased,sampler,d,S", [("wmrb", True, "device", 64, 40), ("balanced_wmrb", False, "replay", 32, 25),
-                                                     ("wmrb", True, "replay", 128, 60), ("wmrb", True, "device", 20, 7)])
-def test_single_kernel_step_equals_multi_launch_steps(loss, biased, sampler, d, S, monkeypatch):
+@pytest.mark.parametrize("loss,biased,sampler,d,S,clocks", [
+    ("wmrb", True, "device", 64, 40, 0), ("balanced_wmrb", False, "replay", 32, 25, 0), ("wmrb", True, "replay", 128, 60, 0),
+    ("wmrb", True, "device", 20, 7, 0), ("wmrb", True, "device", 64, 40, 1)],
+    ids=["wmrb-True-device-64-40", "balanced_wmrb-False-replay-32-25", "wmrb-True-replay-128-60", "wmrb-True-device-20-7",
+         "wmrb-True-device-64-40-coop_clocks"])
+def test_single_kernel_step_equals_multi_launch_steps(loss, biased, sampler, d, S, clocks, monkeypatch):
     """csrc/step_coop.hip: the whole optimiser step of a model that fits on chip (tensorrec.py:617-622 -- sampling, both towers,
     serial + sampled predictions, WMRB, autodiff, Adam) as ONE cooperative kernel, against the same fit made of separate launches:
     the same step and sample counters, the same weights up to summation order -- with the samples drawn INSIDE the kernel (device
     sampler: the bits of trec_sample_items, or the fits would diverge within a step) and with replayed tables; item features with
-    side columns, a user without interactions, negative interactions."""
+    side columns, a user without interactions, negative interactions.  ``clocks``: tuning coop_clocks = 1, the diagnostic clock
+    stamps written into the workspace -- behind every array of the step (n_users and n_items not multiples of 4: the padded
+    bias-gradient tails)."""
     import tensorrec_amd.tensorrec as TT
     rng = np.random.default_rng(11)
     n_users, n_items, steps = 150, 333, 7
@@ -677,6 +682,7 @@ def test_single_kernel_step_equals_multi_launch_steps(loss, biased, sampler, d, 
     out = []
     for coop in (1, 0):
         T._native.set_tuning("fit_step_coop", coop)
+        T._native.set_tuning("coop_clocks", clocks if coop else 0)
         try:
             kw = {"sampler": T.ReplaySampler(tables)} if sampler == "replay" else {}
             model = T.TensorRec(n_components=d, loss_graph=LOSS[loss](), biased=biased, seed=9, hip_graphs=False, **kw)
@@ -689,6 +695,7 @@ def test_single_kernel_step_equals_multi_launch_steps(loss, biased, sampler, d, 
             out.append((g2, model._opt_step, model._sample_step, model.predict(uf, itf)))
         finally:
             T._native.set_tuning("fit_step_coop", 1)
+            T._native.set_tuning("coop_clocks", 0)
         if coop:
             assert calls["run"] == steps - 1, calls                  # (every step but the first)
     (ga, oa, sa, pa), (gb, ob, sb, pb) = out

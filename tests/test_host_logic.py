@@ -193,6 +193,19 @@ def test_abi_pure_queries_and_argument_errors():
     assert rc == 1 and b"null pointer" in lib.trec_last_error()
 
 
+def test_single_kernel_step_workspace_holds_the_padded_arrays_and_the_clocks():
+    """csrc/step_coop.hip: the workspace size counts every array as the kernel lays it out -- item and user bias tails padded to
+    4 floats (f32x4 stores) -- and the 16 floats of clock stamps (tuning coop_clocks) behind the padded item-bias gradient."""
+    def pad4(n):
+        return (n + 3) // 4 * 4
+    for n_users, n_items, d in ((150, 333, 64), (149, 331, 20), (152, 336, 128), (1, 1, 4)):
+        need = _native.query("trec_fit_step_coop_workspace_floats", n_users, n_items, d, 1, 0)
+        layout = (n_items * d + pad4(n_items) + n_users * pad4(n_items) + n_users * d + pad4(n_users) + n_items * d
+                  + pad4(n_items) + 16)
+        assert need == layout, (n_users, n_items, d, need, layout)
+    assert _native.query("trec_fit_step_coop_workspace_floats", 150, 333, 130, 1, 0) == -1      # (d > 128: not covered)
+
+
 def test_no_oracle_in_product():
     """The product package must never import / load anything under oracle/ (the judge checks exactly this)."""
     pkg = os.path.join(ROOT, "tensorrec_amd")
