@@ -249,20 +249,15 @@ int trec_score_prep_filter(const float* repr, int64_t n, int32_t d, int32_t kpad
  *     wg_scale / wg_class [workgroups of the launch] (nullable: scales[0], one bias table): the users' scale and class.
  *     With user_err / chunk_top / top_k (10 or 16): chunk_top [n_chunks_eff * top_k][bm_stride] = per chunk of superblocks
  *     and user the top_k largest lower bounds (sorted, -inf padded); trec_topk_select_blocks over it gives tau.
- *   trec_topk_rows_count / trec_topk_rows_fill: the pairs with table[s][u] + e(u, s) >= thr[u] (two floats below),
- *     grouped by superblock by a row-wise stream compaction (the table is superblock-major: no sort).  count: block_off
- *     [n_sb * trec_topk_rows_user_blocks(n_users)], row_total / row_pad [n_sb], pstart int64 [n_sb + 1] -- pstart[n_sb] is the
- *     number of resident rows (a multiple of 512); status int64[2] = {pstart[n_sb], 1 if it exceeds cap_rows}.  fill:
- *     row_user [cap_rows] (user ids ascending inside a superblock, -1 = padding), rblock_chunk [cap_rows / 512] (-1 for
- *     the idle workgroups beyond the kept pairs; all of them after an overflow, which the caller reads from status when
- *     the pipeline has drained and answers with the dense bf16 stage 1).  No host round trip between the stages.
- *   trec_topk_rows_collect: the same compaction in ONE pass -- row_user [n_sb][rcap] with a fixed capacity per superblock
- *     (rcap % 512 == 0), slots handed out by one atomicAdd per (workgroup, row) on row_count [n_sb] (zero-initialised;
- *     ends as the number of users kept, possibly above rcap: status[1]); the order of a superblock's users follows the
- *     atomics (no result depends on it).
+ *   trec_topk_rows_collect: the pairs with table[s][u] + e(u, s) >= thr[u] (two floats below), grouped by superblock by a
+ *     row-wise stream compaction in ONE pass (the table is superblock-major: no sort) -- row_user [n_sb][rcap] with a fixed
+ *     capacity per superblock (rcap % 512 == 0), slots handed out by one atomicAdd per (workgroup, row) on row_count [n_sb]
+ *     (zero-initialised; ends as the number of users kept, possibly above rcap: status[1]); the order of a superblock's users
+ *     follows the atomics (no result depends on it).  (The two-pass count + fill form was removed: 3.4 ms against 2.0 ms for
+ *     the one pass, docs/history/DESIGN_rounds_1_to_5.md.)
  *   trec_score_gemm_blockmax_grouped: the hand-scheduled bf16 stage-1 kernel over those pairs only; workgroup w re-scores
- *     superblock rblock_chunk[w] for its 512 rows and writes blockmax[rblock_chunk[w] * bm_stride + row_user[r]];
- *     wgs_per_row > 0: the layout of trec_topk_rows_collect (rblock_chunk = row_count, superblock = w / wgs_per_row,
+ *     superblock rblock_chunk[w] for its 512 rows and writes blockmax[rblock_chunk[w] * bm_stride + row_user[r]] (row_user
+ *     [n_rows_g], -1 = padding); wgs_per_row > 0: the layout of trec_topk_rows_collect (rblock_chunk = row_count, superblock = w / wgs_per_row,
  *     n_rows_g = n_sb * wgs_per_row * 512). */
 int trec_score_prep_i8(const float* repr, int64_t n, int32_t d, int32_t kpad, int32_t side, float clip_sigmas,
                        int32_t sb_rows, const float* bias, float* scales, double* workspace, void* out_q,
@@ -299,15 +294,6 @@ int trec_user_prep_sorted(const float* repr, int64_t n, int32_t d, int32_t kpad,
                           int32_t* meta, float* out_f32, void* out_bf16, float* row_stats, void* out_q, float* row_stats8,
                           float* bias_sorted, void* stream);
 int trec_fill_zero(void* p, int64_t nbytes, void* stream);
-int32_t trec_topk_rows_user_blocks(int64_t n_users);
-int trec_topk_rows_count(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
-                         const float* user_err, const float* sb_stats, int32_t kdim, int32_t* block_off,
-                         int32_t* row_total, int32_t* row_pad, int64_t* pstart, int64_t cap_rows, int64_t* status,
-                         void* stream);
-int trec_topk_rows_fill(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
-                        const float* user_err, const float* sb_stats, int32_t kdim, const int32_t* block_off,
-                        const int32_t* row_total, const int64_t* pstart, int64_t cap_rows, const int64_t* status,
-                        int32_t* row_user, int32_t* rblock_chunk, void* stream);
 int trec_topk_rows_collect(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
                            const float* user_err, const float* sb_stats, int32_t kdim, int32_t rcap, int32_t* row_count,
                            int32_t* row_user, int64_t* status, void* stream);
@@ -356,21 +342,8 @@ int trec_score_gemm_refine_candidates(const void* users_bf16, const void* items_
  * (1.9M at 1M users, 98k of them with rows); wg_map NULL = the full grid. */
 int trec_topk_rows_wg_map(const int32_t* row_count, int32_t n_sb, int32_t wgs_per_row, int32_t* wg_start, int32_t* wg_map,
                           int64_t map_cap, void* stream);
-/* The same map with group_rows users per workgroup slot instead of 512 (entries beyond wg_start[n_sb] are left as the caller
- * preset them: an id >= n_sb * wgs_per_row is an idle workgroup of trec_score_gemm_refine_candidates_resident). */
-int trec_topk_rows_wg_map_ex(const int32_t* row_count, int32_t n_sb, int32_t wgs_per_row, int32_t group_rows, int32_t* wg_start,
-                             int32_t* wg_map, int64_t map_cap, void* stream);
-/* trec_score_gemm_refine_candidates with the ITEMS resident (csrc/refine_resident.hip; same bf16-path maxima over the table entries,
- * same candidate lists -- tensorrec/prediction_graphs.py:50 + recommendation_graphs.py:41 reduced towards the first tf.nn.top_k of
- * recommendation_graphs.py:80): workgroup w keeps the 512 items of superblock wg_map[w] / segs_per_row in registers and streams
- * segment wg_map[w] % segs_per_row (seg_rows users, a multiple of 64) of its user list row_user [n_sb][rcap] through LDS.
- * sb_rows must be 512; row_count [n_sb] is clamped to rcap (0 = nothing to do: hot superblocks). */
-int trec_score_gemm_refine_candidates_resident(const void* users_bf16, const void* items_bf16, int32_t kpad, int64_t n_items,
-                                               const float* user_bias, const float* item_bias, int32_t sb_rows, int32_t n_sb,
-                                               const int32_t* row_count, const int32_t* row_user, int32_t rcap, float* blockmax,
-                                               int64_t bm_stride, const float* cand_floor, int32_t* cand_n, void* cand,
-                                               int32_t cand_cap, int32_t item_index_base, const int32_t* wg_map, int32_t n_wgs,
-                                               int32_t segs_per_row, int32_t seg_rows, void* stream);
+/* (The item-resident form of the refining launch was removed: on par, not faster -- 1.92 + 2.70 ms against 1.81 + 2.73 ms,
+ * the round-6 A/B record of DESIGN section 5.) */
 int trec_score_gemm_refine_candidates_hot(const void* users_bf16, const void* items_bf16, int32_t kpad, int64_t n_users,
                                           int64_t n_items, const float* user_bias, const float* item_bias, int32_t sb_rows,
                                           const int32_t* hot_list, int32_t hot_cap, float* blockmax, int64_t bm_stride,
@@ -415,25 +388,17 @@ int trec_topk_cascade_floor(float* tau, const int32_t* src, const float* user_st
 
 /* The cascade's PRE-REFINEMENT (csrc/topk_filter.hip): the k superblocks holding a user's k largest int8 lower bounds
  * are refined first; tau = max(tau8, min of their bf16 maxima - eps) is a sharper lower bound of the k-th best score of
- * tf.nn.top_k (recommendation_graphs.py:80) for the compaction and the candidate floor.  trec_topk_prerefine_rows: selection over
- * the chunk lists written with top_k | 0x100 (tagged lower bounds) -> per-superblock user lists (layout of trec_topk_rows_collect)
- * + sel_sb [n_users][k] + ok [n_users]; the bf16 launch over them is trec_score_gemm_refine_candidates (it also lists their
- * candidates; trec_topk_prerefine_tau with listed = 1 then saves the maxima, takes the pairs out of the compaction (-inf) and raises
- * tau and the candidate floor) or trec_score_gemm_blockmax_grouped (listed = 0: the entries become +inf and the listing launch
- * refines them again). */
+ * tf.nn.top_k (recommendation_graphs.py:80) for the compaction and the candidate floor.  trec_topk_prerefine_rows_pos: selection
+ * over the chunk lists written with top_k | 0x100 (tagged lower bounds) -> per-superblock user lists (layout of
+ * trec_topk_rows_collect) + sel_sb [n_users][k] + ok [n_users] + sel_pos [n_users][k], the position of every placed pair inside
+ * its superblock's list.  The bf16 launch over them, trec_score_gemm_refine_candidates_marked, also lists their candidates, leaves
+ * the bf16 maxima in pre_max [n_sb * rcap] by list position and marks the table entries -inf itself (the compaction drops the
+ * pairs: nothing is refined twice); trec_topk_prerefine_tau_listed reads the maxima back from there, saves them to vals
+ * [n_users][k] and raises tau and the candidate floor.  These take k <= 64 (the wide route, 17 <= k <= 64, pre-refines too).
+ * Same reference arithmetic as the refining launches (recommendation_graphs.py:73-82 restricted to what the exact top-k needs).
+ * (Removed: the maxima-only form that refined the pairs again, and the table pass behind an unmarked launch -- 0.94 against
+ * 0.61 ms, the round-6 A/B record of DESIGN section 5.) */
 int32_t trec_topk_prerefine_max_superblocks(void);
-int trec_topk_prerefine_rows(const int32_t* sel, const float* sel_val, int32_t k, int32_t top_k, int32_t sb_per_chunk, int32_t n_sb,
-                             int64_t n_users, const int32_t* src, int32_t rcap, int32_t* sel_sb, int32_t* row_count,
-                             int32_t* row_user, int32_t* ok, void* stream);
-int trec_topk_prerefine_tau(const int32_t* sel_sb, const int32_t* ok, int32_t k, float* table, int64_t stride, int64_t n_users,
-                            const int32_t* src, const float* user_stats, const float* user_bias, const float* item_gstats,
-                            int32_t kdim, float* tau, int32_t listed, float* vals, float* cand_floor, void* stream);
-/* The pre-refinement without a table pass behind its launch (round 6): trec_topk_prerefine_rows_pos also records sel_pos [n_users][k],
- * the position of every placed pair inside its superblock's list; trec_score_gemm_refine_candidates_marked (declared with the other
- * refining launches) leaves the bf16 maxima in pre_max [n_sb * rcap] by list position and marks the table entries -inf itself;
- * trec_topk_prerefine_tau_listed reads the maxima back from there (vals, tau, cand_floor as trec_topk_prerefine_tau with listed != 0).
- * These two take k <= 64 (the wide route, 17 <= k <= 64, pre-refines too); trec_topk_prerefine_rows / _tau keep k <= 16.
- * Same reference arithmetic as the calls they replace (recommendation_graphs.py:73-82 restricted to what the exact top-k needs). */
 int trec_topk_prerefine_rows_pos(const int32_t* sel, const float* sel_val, int32_t k, int32_t top_k, int32_t sb_per_chunk,
                                  int32_t n_sb, int64_t n_users, const int32_t* src, int32_t rcap, int32_t* sel_sb,
                                  int32_t* row_count, int32_t* row_user, int32_t* ok, int32_t* sel_pos, void* stream);

@@ -74,12 +74,7 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "trec_fill_zero": [_vp, _i64, _vp],
     "trec_topk_cascade_floor": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
-    "trec_topk_rows_user_blocks": [_i64],
-    "trec_topk_rows_count": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
-    "trec_topk_rows_fill": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "trec_topk_prerefine_max_superblocks": [],
-    "trec_topk_prerefine_rows": [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    "trec_topk_prerefine_tau": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp],
     "trec_topk_prerefine_rows_pos": [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "trec_topk_prerefine_tau_listed": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "trec_score_gemm_refine_candidates_marked": [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
@@ -92,9 +87,6 @@ SIGNATURES = {
     "trec_score_gemm_refine_candidates": [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
                                           _i32, _i32, _vp, _i32, _vp],
     "trec_topk_rows_wg_map": [_vp, _i32, _i32, _vp, _vp, _i64, _vp],
-    "trec_topk_rows_wg_map_ex": [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp],
-    "trec_score_gemm_refine_candidates_resident": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp,
-                                                   _i32, _i32, _vp, _i32, _i32, _i32, _vp],
     "trec_score_gemm_refine_candidates_hot": [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp,
                                               _i32, _i32, _vp],
     "trec_topk_candidates_finish": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i32, _i64, _i32, _vp,

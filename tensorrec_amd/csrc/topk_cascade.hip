@@ -5,12 +5,15 @@
 //   select   trec_topk_select_blocks over the chunks' lists (k rows per chunk, not the table): tauLB_u = the k-th largest
 //            lower bound.  e(u, s) >= |int8 score - fp32 score| for every item of superblock s: proven from the MEASURED
 //            quantisation error norms of trec_score_prep_i8, per user and per superblock (i8_pair_err, score_common.hpp)
-//   compact  trec_topk_rows_count / trec_topk_rows_fill (here): the (superblock, user) pairs whose UPPER bound M8 + e(u, s)
-//            reaches tauLB_u, already grouped by superblock -- the table is superblock-major, so a row-wise stream
-//            compaction IS the grouping (no sort): per superblock a run of user ids padded with -1 to whole 512-row workgroups
-//   stage 1  trec_score_gemm_blockmax_grouped (here + score_blockmax.hip): the hand-scheduled bf16 kernel on the kept pairs
-//            only (~4% of them at 1M x 1M); each bf16 maximum REPLACES the int8 entry of the table
-//   then the bf16 filter of topk_filter.hip runs unchanged on the mixed table (select, floor16, collect, bf16 lists, fp32).
+//   compact  trec_topk_rows_collect (here): the (superblock, user) pairs whose UPPER bound M8 + e(u, s) reaches tauLB_u, in
+//            ONE pass over the table, already grouped by superblock -- the table is superblock-major, so a row-wise stream
+//            compaction IS the grouping (no sort): per superblock a list of user ids with a fixed capacity
+//   stage 1  trec_score_gemm_refine_candidates / trec_score_gemm_blockmax_grouped (here + score_blockmax.hip): the
+//            hand-scheduled bf16 kernel on the kept pairs only (~4% of them at 1M x 1M); each bf16 maximum REPLACES the int8
+//            entry of the table, and the listing form also lists every item that can still reach the top-k
+//   then trec_topk_candidates_finish of topk_filter.hip finishes from those lists -- or, without them, the bf16 filter of
+//   topk_filter.hip runs unchanged on the mixed table (select, floor16, collect, bf16 lists, fp32).
+//   (The two-pass count + fill compaction was removed: one pass took 2.0 ms against 3.4 ms, docs/history/DESIGN_rounds_1_to_5.md.)
 //
 // Nothing is lost: k superblocks have M8 - e >= tauLB, each holds an item with fp32 score >= tauLB, so the true k-th best
 // t_k >= tauLB.  A top-k item has fp32 score >= t_k >= tauLB and int8 score >= fp32 - e, so its superblock has
@@ -112,168 +115,7 @@ __device__ __forceinline__ unsigned int tile_bits(const float* __restrict__ tabl
     return bits;
 }
 
-// A workgroup owns 1024 users x CGROUPS groups of CROWS table rows: the users' constants are loaded once (per 8-row group
-// they were half as many bytes again as the table itself).
-__global__ __launch_bounds__(256) void rows_count_kernel(const float* __restrict__ table, int32_t n_sb, int64_t n_users,
-                                                        int64_t stride, const float* __restrict__ thr,
-                                                        const float* __restrict__ user_err,
-                                                        const float* __restrict__ sb_stats, int kdim, int32_t n_ublk,
-                                                        int32_t* __restrict__ blockcnt)
-{
-    __shared__ int cnt[CGROUPS][CROWS];
-    if (threadIdx.x < CGROUPS * CROWS) (&cnt[0][0])[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t u = (int64_t)blockIdx.x * CUSERS + threadIdx.x * 4;
-    const UserConsts c = load_user_consts(thr, user_err, n_users, u);
-    for (int g = 0; g < CGROUPS; ++g) {
-        const int32_t s0 = (blockIdx.y * CGROUPS + g) * CROWS;
-        if (s0 >= n_sb) break;
-        const unsigned int bits = tile_bits(table, n_sb, n_users, stride, c, sb_stats, kdim, s0, u);
-#pragma unroll
-        for (int r = 0; r < CROWS; ++r) {
-            int k = __builtin_popcount((bits >> (4 * r)) & 15u);
-            for (int off = 32; off > 0; off >>= 1) k += __shfl_xor(k, off, 64);
-            if ((threadIdx.x & 63) == 0 && k) atomicAdd(&cnt[g][r], k);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < CGROUPS * CROWS) {
-        const int32_t s = blockIdx.y * CGROUPS * CROWS + threadIdx.x;
-        if (s < n_sb) blockcnt[(int64_t)s * n_ublk + blockIdx.x] = (&cnt[0][0])[threadIdx.x];
-    }
-}
-
-// one workgroup per table row: exclusive scan of the row's block counts in place, the row's total and its padded size
-__global__ __launch_bounds__(256) void rows_scan_kernel(int32_t* __restrict__ blockcnt, int32_t n_ublk,
-                                                       int32_t* __restrict__ row_total, int32_t* __restrict__ row_pad)
-{
-    __shared__ int wsum[4];
-    __shared__ int carry_s;
-    const int s = blockIdx.x;
-    int32_t* row = blockcnt + (int64_t)s * n_ublk;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < n_ublk; b0 += 256) {
-        const int b = b0 + threadIdx.x;
-        const int c = b < n_ublk ? row[b] : 0;
-        int inc = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(inc, off, 64);
-            if ((threadIdx.x & 63) >= off) inc += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        int base = carry_s;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-        if (b < n_ublk) row[b] = base + inc - c;
-        __syncthreads();
-        if (threadIdx.x == 255) carry_s = base + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        row_total[s] = carry_s;
-        row_pad[s] = (carry_s + GROUP_ROWS - 1) / GROUP_ROWS * GROUP_ROWS;
-    }
-}
-
-// single workgroup: pstart[s] = sum of the padded sizes of rows < s, pstart[n_sb] = the grouped launch's resident rows
-// status[0] = pstart[n_sb], status[1] = 1 when that exceeds cap_rows (the caller's row_user capacity): pass 2 and the grouped
-// launch then do nothing and the caller falls back to the dense bf16 stage 1
-__global__ __launch_bounds__(256) void rows_pstart_kernel(const int32_t* __restrict__ row_pad, int32_t n_sb,
-                                                         int64_t* __restrict__ pstart, int64_t cap_rows,
-                                                         int64_t* __restrict__ status)
-{
-    __shared__ long long wsum[4];
-    __shared__ long long carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < n_sb; s0 += 256) {
-        const int s = s0 + threadIdx.x;
-        const long long c = s < n_sb ? row_pad[s] : 0;
-        long long inc = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(inc, off, 64);
-            if ((threadIdx.x & 63) >= off) inc += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        long long base = carry_s;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wsum[w];
-        if (s < n_sb) pstart[s] = base + inc - c;
-        __syncthreads();
-        if (threadIdx.x == 255) carry_s = base + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        pstart[n_sb] = carry_s;
-        status[0] = carry_s;
-        status[1] = carry_s > cap_rows ? 1 : 0;
-    }
-}
-
-// workgroups of the grouped launch beyond the kept pairs (all of them after an overflow) are idle: superblock id -1
-__global__ __launch_bounds__(256) void rows_tail_kernel(const int64_t* __restrict__ status, int64_t cap_wgs,
-                                                       int32_t* __restrict__ rblock_chunk)
-{
-    const int64_t first = status[1] ? 0 : status[0] / GROUP_ROWS;
-    for (int64_t w = first + (int64_t)blockIdx.x * 256 + threadIdx.x; w < cap_wgs; w += (int64_t)gridDim.x * 256)
-        rblock_chunk[w] = -1;
-}
-
-__global__ __launch_bounds__(256) void rows_fill_kernel(const float* __restrict__ table, int32_t n_sb, int64_t n_users,
-                                                       int64_t stride, const float* __restrict__ thr,
-                                                       const float* __restrict__ user_err,
-                                                       const float* __restrict__ sb_stats, int kdim, int32_t n_ublk,
-                                                       const int32_t* __restrict__ blockoff,
-                                                       const int32_t* __restrict__ row_total,
-                                                       const int64_t* __restrict__ pstart, int32_t* __restrict__ row_user,
-                                                       int32_t* __restrict__ rblock_chunk, const int64_t* __restrict__ status)
-{
-    __shared__ int wsum[2][CROWS][4];
-    if (status[1]) return;                                       // more pairs than row_user holds: nothing is refined
-    const int64_t u = (int64_t)blockIdx.x * CUSERS + threadIdx.x * 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const UserConsts c = load_user_consts(thr, user_err, n_users, u);
-    for (int g = 0; g < CGROUPS; ++g) {
-        const int32_t s0 = (blockIdx.y * CGROUPS + g) * CROWS;
-        if (s0 >= n_sb) break;
-        const unsigned int bits = tile_bits(table, n_sb, n_users, stride, c, sb_stats, kdim, s0, u);
-        int pre[CROWS];
-#pragma unroll
-        for (int r = 0; r < CROWS; ++r) {
-            const int k = __builtin_popcount((bits >> (4 * r)) & 15u);
-            int inc = k;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += t;
-            }
-            pre[r] = inc - k;
-            if (lane == 63) wsum[g & 1][r][wave] = inc;
-        }
-        __syncthreads();                                         // (two alternating buffers: one barrier per group is enough)
-#pragma unroll
-        for (int r = 0; r < CROWS; ++r) {
-            const int32_t s = s0 + r;
-            if (s >= n_sb) break;
-            const unsigned int m = (bits >> (4 * r)) & 15u;
-            if (m) {
-                int base = pre[r];
-                for (int w = 0; w < wave; ++w) base += wsum[g & 1][r][w];
-                int64_t dst = pstart[s] + blockoff[(int64_t)s * n_ublk + blockIdx.x] + base;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if ((m >> e) & 1u) row_user[dst++] = (int32_t)(u + e);
-            }
-            if (blockIdx.x == 0) {                               // the row's padding entries and its workgroups' superblock ids
-                const int64_t p0 = pstart[s], p1 = pstart[s + 1];
-                for (int64_t j = p0 + row_total[s] + threadIdx.x; j < p1; j += 256) row_user[j] = -1;
-                for (int64_t w = p0 / GROUP_ROWS + threadIdx.x; w < p1 / GROUP_ROWS; w += 256) rblock_chunk[w] = s;
-            }
-        }
-    }
-}
-
-// ---- the same compaction in ONE pass over the table: fixed capacity per superblock --------------------------------------
+// ---- the compaction in ONE pass over the table: fixed capacity per superblock -------------------------------------------
 // row_user is [n_sb][rcap]; a workgroup (1024 users x 32 rows) takes, per row, a run of slots with ONE atomicAdd on the row's
 // counter and writes its kept users there (ascending inside the run; the order of the runs of different workgroups follows
 // the atomics -- which users share a workgroup of the bf16 stage changes from run to run, no result does).  Slots beyond
@@ -495,53 +337,7 @@ __global__ __launch_bounds__(256) void rows_hot_kernel(int32_t* __restrict__ row
 
 }  // namespace
 
-extern "C" int32_t trec_topk_rows_user_blocks(int64_t n_users) { return (int32_t)ceil_div64(n_users, CUSERS); }
-
-// pass 1 of the row-wise compaction: block_off [n_sb][trec_topk_rows_user_blocks(n_users)] (scratch for pass 2),
-// row_total [n_sb], pstart [n_sb + 1] (int64; pstart[n_sb] = resident rows of the grouped launch, a multiple of 512),
-// status int64[2] = {pstart[n_sb], overflow: it exceeds cap_rows} -- nothing here needs the host
-extern "C" int trec_topk_rows_count(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
-                                    const float* user_err, const float* sb_stats, int32_t kdim, int32_t* block_off,
-                                    int32_t* row_total, int32_t* row_pad, int64_t* pstart, int64_t cap_rows,
-                                    int64_t* status, void* stream)
-{
-    TREC_REQUIRE(table && thr && user_err && sb_stats && block_off && row_total && row_pad && pstart && status,
-                 "trec_topk_rows_count: null pointer");
-    TREC_REQUIRE(cap_rows >= 0 && cap_rows % GROUP_ROWS == 0, "trec_topk_rows_count: cap_rows must be a multiple of 512");
-    TREC_REQUIRE(n_sb >= 1 && n_users >= 1 && stride >= n_users, "trec_topk_rows_count: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    const int n_ublk = (int)ceil_div64(n_users, CUSERS);
-    hipLaunchKernelGGL(rows_count_kernel, dim3((unsigned)n_ublk, (unsigned)((n_sb + CROWS * CGROUPS - 1) / (CROWS * CGROUPS))), dim3(256), 0, st,
-                       table, n_sb, n_users, stride, thr, user_err, sb_stats, kdim, n_ublk, block_off);
-    hipLaunchKernelGGL(rows_scan_kernel, dim3((unsigned)n_sb), dim3(256), 0, st, block_off, n_ublk, row_total, row_pad);
-    hipLaunchKernelGGL(rows_pstart_kernel, dim3(1), dim3(256), 0, st, row_pad, n_sb, pstart, cap_rows, status);
-    return trec_check_launch("trec_topk_rows_count");
-}
-
-// pass 2: row_user [cap_rows], first pstart[n_sb] entries = the kept users of superblock 0, padding (-1), those of
-// superblock 1, ... (ascending user ids inside a superblock); rblock_chunk [cap_rows / 512] = the superblock of each
-// 512-row workgroup, -1 for the workgroups beyond pstart[n_sb] / 512 (all of them when status[1] is set)
-extern "C" int trec_topk_rows_fill(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
-                                   const float* user_err, const float* sb_stats, int32_t kdim, const int32_t* block_off,
-                                   const int32_t* row_total, const int64_t* pstart, int64_t cap_rows, const int64_t* status,
-                                   int32_t* row_user, int32_t* rblock_chunk, void* stream)
-{
-    TREC_REQUIRE(table && thr && user_err && sb_stats && block_off && row_total && pstart && status && row_user && rblock_chunk,
-                 "trec_topk_rows_fill: null pointer");
-    TREC_REQUIRE(cap_rows >= GROUP_ROWS && cap_rows % GROUP_ROWS == 0, "trec_topk_rows_fill: cap_rows must be a multiple of 512");
-    TREC_REQUIRE(n_sb >= 1 && n_users >= 1 && stride >= n_users, "trec_topk_rows_fill: bad sizes");
-    const int n_ublk = (int)ceil_div64(n_users, CUSERS);
-    hipLaunchKernelGGL(rows_fill_kernel, dim3((unsigned)n_ublk, (unsigned)((n_sb + CROWS * CGROUPS - 1) / (CROWS * CGROUPS))), dim3(256), 0,
-                       (hipStream_t)stream, table, n_sb, n_users, stride, thr, user_err, sb_stats, kdim, n_ublk, block_off,
-                       row_total, pstart, row_user, rblock_chunk, status);
-    const int64_t cap_wgs = cap_rows / GROUP_ROWS;
-    unsigned tb = (unsigned)ceil_div64(cap_wgs, 256);
-    if (tb > 1024) tb = 1024;
-    hipLaunchKernelGGL(rows_tail_kernel, dim3(tb), dim3(256), 0, (hipStream_t)stream, status, cap_wgs, rblock_chunk);
-    return trec_check_launch("trec_topk_rows_fill");
-}
-
-// The one-pass form of the compaction: row_user [n_sb][rcap] (rcap a multiple of 512), row_count [n_sb] zero-initialised by
+// The compaction: row_user [n_sb][rcap] (rcap a multiple of 512), row_count [n_sb] zero-initialised by
 // the caller (ends as the number of users kept per superblock, possibly above rcap), status int64[2] = {resident rows,
 // overflow}.  The order of a superblock's users is not deterministic (runs of ascending ids in atomic order).
 extern "C" int trec_topk_rows_collect(const float* table, int32_t n_sb, int64_t n_users, int64_t stride, const float* thr,
@@ -797,19 +593,4 @@ extern "C" int trec_topk_rows_wg_map(const int32_t* row_count, int32_t n_sb, int
     hipLaunchKernelGGL(wg_start_kernel, dim3(1), dim3(256), 0, st, row_count, n_sb, wgs_per_row, wg_start, GROUP_ROWS);
     hipLaunchKernelGGL(wg_map_kernel, dim3((unsigned)n_sb), dim3(256), 0, st, wg_start, wgs_per_row, map_cap, wg_map);
     return trec_check_launch("trec_topk_rows_wg_map");
-}
-
-// The same map with group_rows users per workgroup slot instead of 512 (the item-resident refining launch,
-// trec_score_gemm_refine_candidates_resident: segments of 2,048 users): wg_map[wg_start[s] + j] = s * wgs_per_row + j for
-// j < min(ceil(row_count[s] / group_rows), wgs_per_row); entries beyond wg_start[n_sb] are not written (the caller presets them idle).
-extern "C" int trec_topk_rows_wg_map_ex(const int32_t* row_count, int32_t n_sb, int32_t wgs_per_row, int32_t group_rows,
-                                        int32_t* wg_start, int32_t* wg_map, int64_t map_cap, void* stream)
-{
-    TREC_REQUIRE(row_count && wg_start && wg_map, "trec_topk_rows_wg_map_ex: null pointer");
-    TREC_REQUIRE(n_sb >= 1 && wgs_per_row >= 1 && group_rows >= 1 && map_cap >= 0 && (int64_t)n_sb * wgs_per_row < ((int64_t)1 << 31),
-                 "trec_topk_rows_wg_map_ex: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(wg_start_kernel, dim3(1), dim3(256), 0, st, row_count, n_sb, wgs_per_row, wg_start, group_rows);
-    hipLaunchKernelGGL(wg_map_kernel, dim3((unsigned)n_sb), dim3(256), 0, st, wg_start, wgs_per_row, map_cap, wg_map);
-    return trec_check_launch("trec_topk_rows_wg_map_ex");
 }

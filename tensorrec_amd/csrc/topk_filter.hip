@@ -278,62 +278,13 @@ __global__ __launch_bounds__(256) void prerefine_rows_kernel(const int32_t* __re
     }
 }
 
-// After the pre-refining launch: tau[u] = max(tau[u], min_j table[sel_sb[u][j]][u] - eps_u) for the users with ok[u] (all k slots
-// placed).  Then the listed entries are taken out of the compaction's way:
-//   listed == 0 (the pre-refining launch only wrote maxima): every listed entry becomes +inf -- the compaction keeps those pairs
-//     whatever its own bound says and the listing launch refines them again; a refined entry is never compared through the int8
-//     bound e, which need not cover eps;
-//   listed != 0 (it also LISTED their candidates, trec_score_gemm_refine_candidates with the provisional floor tau8 - eps): the
-//     bf16 maxima are saved to vals [n_users][k], the entries become -inf -- the compaction drops the pairs, nothing is refined
-//     twice.  The caller puts vals back into the columns of the users it has to re-do from the table.
-// Either way cand_floor[u] (nullable) rises to tau - eps for the launches still to come (a user that lists nothing keeps +inf).
-__global__ __launch_bounds__(256) void prerefine_tau_kernel(const int32_t* __restrict__ sel_sb, const int32_t* __restrict__ ok, int k,
-                                                           float* __restrict__ table, int64_t stride, int64_t n_users,
-                                                           const int32_t* __restrict__ src, const float2* __restrict__ ustats,
-                                                           const float* __restrict__ user_bias, const float* __restrict__ gstats,
-                                                           int kdim, float* __restrict__ tau, int listed, float* __restrict__ vals,
-                                                           float* __restrict__ cand_floor)
-{
-    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= n_users) return;
-    const bool live = !(src && src[u] < 0);
-    float m = INFINITY;
-    int32_t s[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s[j] = (live && j < k) ? sel_sb[u * k + j] : -1;
-    float v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = s[j] >= 0 ? table[(int64_t)s[j] * stride + u] : INFINITY;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m = fminf(m, (v[j] == v[j]) ? v[j] : -INFINITY);          // a NaN certifies nothing
-    if (listed) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) if (j < k) vals[u * k + j] = v[j];
-    }
-    if (!live) return;
-    if (ok[u]) {
-        const float eps = filter_eps(ustats[u], user_bias ? fabsf(user_bias[u]) : 0.f, gstats, kdim);
-        float t = m - eps;
-        if (eps < INFINITY && t == t && m < INFINITY) {
-            t = float_pred(float_pred(t));
-            if (t > tau[u]) {
-                tau[u] = t;
-                if (cand_floor && cand_floor[u] < INFINITY) {
-                    const float f = float_pred(float_pred(t - eps));           // the provisional floor of the launches to come
-                    if (f > cand_floor[u]) cand_floor[u] = f;
-                }
-            }
-        }
-    }
-    const float mark = listed ? -INFINITY : INFINITY;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (s[j] >= 0) table[(int64_t)s[j] * stride + u] = mark;
-}
-
-// The same threshold step behind the MARKING pre-refining launch (trec_score_gemm_refine_candidates_marked): the maxima are read back from
-// the lists -- pre_max[sel_sb * rcap + sel_pos], a few tens of MB that the launch has just written -- instead of from 10 random
-// entries per user of the 7.8 GB table, and the -inf marks are already in place: no table access at all (0.54 -> ~0.2 ms at 1M users).
+// After the MARKING pre-refining launch (trec_score_gemm_refine_candidates_marked, which also LISTED the pairs' candidates with the
+// provisional floor tau8 - eps): tau[u] = max(tau[u], min_j M16 - eps_u) for the users with ok[u] (all k slots placed).  The maxima
+// are read back from the lists -- pre_max[sel_sb * rcap + sel_pos], a few tens of MB that the launch has just written -- instead of
+// from 10 random entries per user of the 7.8 GB table, and the launch has already marked the table entries -inf (the compaction
+// drops the pairs, nothing is refined twice): no table access at all (0.54 -> ~0.2 ms at 1M users).  The maxima are saved to
+// vals [n_users][k]: the caller puts them back into the columns of the users it has to re-do from the table.  cand_floor[u]
+// (nullable) rises to tau - eps for the launches still to come (a user that lists nothing keeps +inf).
 __global__ __launch_bounds__(256) void prerefine_tau_listed_kernel(const int32_t* __restrict__ sel_sb, const int32_t* __restrict__ sel_pos,
                                                                   const int32_t* __restrict__ ok, int k, const float* __restrict__ pre_max,
                                                                   int64_t rcap, int64_t n_users, const int32_t* __restrict__ src,
@@ -1259,25 +1210,12 @@ extern "C" int trec_topk_cascade_floor(float* tau, const int32_t* src, const flo
 // The cascade's pre-refinement, step 1 (prerefine_rows_kernel): from the selection over the TAGGED chunk lists (sel [n_users][k]
 // rows, sel_val [k][n_users] values; lists written with top_k | 0x100) to per-superblock user lists in the fixed-capacity layout of
 // trec_topk_rows_collect (row_count [n_sb] zeroed by the caller, row_user [n_sb][rcap], rcap % 512 == 0) for
-// trec_score_gemm_blockmax_grouped, plus sel_sb [n_users][k] (superblock ids, -1 = empty slot) and ok [n_users].
+// trec_score_gemm_refine_candidates_marked, plus sel_sb [n_users][k] (superblock ids, -1 = empty slot) and ok [n_users].
 // n_sb * 4 bytes of LDS: n_sb <= trec_topk_prerefine_max_superblocks().
 extern "C" int32_t trec_topk_prerefine_max_superblocks(void) { return 16000; }
 
-extern "C" int trec_topk_prerefine_rows(const int32_t* sel, const float* sel_val, int32_t k, int32_t top_k, int32_t sb_per_chunk,
-                                        int32_t n_sb, int64_t n_users, const int32_t* src, int32_t rcap, int32_t* sel_sb,
-                                        int32_t* row_count, int32_t* row_user, int32_t* ok, void* stream)
-{
-    TREC_REQUIRE(sel && sel_val && sel_sb && row_count && row_user && ok, "trec_topk_prerefine_rows: null pointer");
-    TREC_REQUIRE(k >= 1 && k <= 16 && top_k >= 1 && sb_per_chunk >= 1 && sb_per_chunk <= (1 << TREC_LB_TAG_BITS) && n_sb >= 1 &&
-                 n_sb <= trec_topk_prerefine_max_superblocks() && rcap >= 512 && rcap % 512 == 0, "trec_topk_prerefine_rows: bad sizes");
-    if (n_users == 0) return TREC_OK;
-    hipLaunchKernelGGL(prerefine_rows_kernel<16>, dim3((unsigned)ceil_div64(n_users, 1024)), dim3(256), (size_t)n_sb * 4, (hipStream_t)stream,
-                       sel, sel_val, k, top_k, sb_per_chunk, n_sb, n_users, src, rcap, sel_sb, row_count, row_user, ok, (int32_t*)nullptr);
-    return trec_check_launch("trec_topk_prerefine_rows");
-}
-
-// ... and with sel_pos [n_users][k]: the position of every placed (user, slot) pair inside its superblock's list (undefined where
-// sel_sb is -1) -- what trec_topk_prerefine_tau_listed reads the maxima back by.
+// sel_pos [n_users][k]: the position of every placed (user, slot) pair inside its superblock's list (undefined where sel_sb is -1)
+// -- what trec_topk_prerefine_tau_listed reads the maxima back by.
 extern "C" int trec_topk_prerefine_rows_pos(const int32_t* sel, const float* sel_val, int32_t k, int32_t top_k, int32_t sb_per_chunk,
                                             int32_t n_sb, int64_t n_users, const int32_t* src, int32_t rcap, int32_t* sel_sb,
                                             int32_t* row_count, int32_t* row_user, int32_t* ok, int32_t* sel_pos, void* stream)
@@ -1312,24 +1250,4 @@ extern "C" int trec_topk_prerefine_tau_listed(const int32_t* sel_sb, const int32
                        sel_pos, ok, k, pre_max, (int64_t)rcap, n_users, src, (const float2*)user_stats, user_bias, item_gstats, kdim, tau,
                        vals, cand_floor);
     return trec_check_launch("trec_topk_prerefine_tau_listed");
-}
-
-// Step 2, after the bf16 launch over those lists (prerefine_tau_kernel): tau [n_users] IN / OUT is raised to
-// min_j table[sel_sb[u][j]][u] - eps_u where that is larger (users with ok[u]).  listed == 0 (the launch was
-// trec_score_gemm_blockmax_grouped): every listed table entry becomes +inf.  listed != 0 (trec_score_gemm_refine_candidates, which
-// also listed the candidates): vals [n_users][k] receives the bf16 maxima, the entries become -inf (the compaction drops the pairs)
-// and cand_floor [n_users] rises to the new tau - eps where it was finite.
-extern "C" int trec_topk_prerefine_tau(const int32_t* sel_sb, const int32_t* ok, int32_t k, float* table, int64_t stride,
-                                       int64_t n_users, const int32_t* src, const float* user_stats, const float* user_bias,
-                                       const float* item_gstats, int32_t kdim, float* tau, int32_t listed, float* vals,
-                                       float* cand_floor, void* stream)
-{
-    TREC_REQUIRE(sel_sb && ok && table && user_stats && item_gstats && tau && k >= 1 && k <= 16 && stride >= n_users,
-                 "trec_topk_prerefine_tau: bad arguments");
-    TREC_REQUIRE(!listed || vals, "trec_topk_prerefine_tau: the listed form needs vals");
-    if (n_users == 0) return TREC_OK;
-    hipLaunchKernelGGL(prerefine_tau_kernel, dim3((unsigned)ceil_div64(n_users, 256)), dim3(256), 0, (hipStream_t)stream, sel_sb, ok, k,
-                       table, stride, n_users, src, (const float2*)user_stats, user_bias, item_gstats, kdim, tau, listed, vals,
-                       cand_floor);
-    return trec_check_launch("trec_topk_prerefine_tau");
 }

@@ -561,55 +561,11 @@ def blockmax_i8_chunks(n_items, n_chunks, sb_rows):
     return chunk_len, -(-n_items // chunk_len)
 
 
-import contextlib as _contextlib
-
-
-@_contextlib.contextmanager
-def _tail_of(tail_stream, *tensors):
-    """Launches inside run on ``tail_stream`` (None: the current one) once everything queued on the current stream so far is
-    done; ``tensors`` -- allocated on the current stream, used inside -- are recorded on it so that the allocator does not hand
-    their memory out again before the tail stream is through with them."""
-    if tail_stream is None:
-        yield
-        return
-    tail_stream.wait_stream(torch.cuda.current_stream())
-    for t in tensors:
-        if t is not None:
-            t.record_stream(tail_stream)
-    with torch.cuda.stream(tail_stream):
-        yield
-
-
-class _Pending(object):
-    """A filtered top-k whose tail is still running on another stream: ``complete()`` -- once the caller's stream has waited
-    for that stream -- reads the flagged-user counter, re-does those users and returns (values, ids, stats)."""
-    __slots__ = ("complete",)
-
-    def __init__(self, complete):
-        self.complete = complete
-
-
 class _Candidates(object):
     """What the refining launches listed (trec_score_gemm_refine_candidates): per user ``n`` appended entries of ``items``
     [n_users, cap, 2] = {item id, score bits}, made with the provisional floor ``floor0`` (+inf: nothing listed); ``flag`` /
     ``n_flagged``: users without a usable bound so far."""
     __slots__ = ("n", "items", "cap", "floor0", "flag", "n_flagged", "pre")
-
-
-RESIDENT_SEGMENT = 2048          # users of a superblock's list one workgroup of the item-resident refining launch streams
-
-
-def _refine_resident(sb_rows, kpad):
-    """tuning refine_resident = 1: the refining launches keep the ITEMS resident (csrc/refine_resident.hip; the superblock must be
-    the 512 items its four waves hold).  Measured on par with the user-resident kernel, not faster (1.92 + 2.70 against 1.81 + 2.73 ms
-    at 1M x 1M, profiles/r06_refine_resident_ab.txt): the default stays the user-resident kernel, this one is the A/B alternative."""
-    return int(sb_rows) == 512 and kpad in (64, 128) and N.load().trec_get_tuning(b"refine_resident", 0) != 0
-
-
-def _resident_segments(rcap):
-    seg = int(N.load().trec_get_tuning(b"refine_resident_seg", RESIDENT_SEGMENT))
-    seg = max(64, seg // 64 * 64)
-    return seg, (int(rcap) + seg - 1) // seg
 
 
 def cascade_lists_candidates():
@@ -620,7 +576,7 @@ def cascade_lists_candidates():
 
 
 def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, floor_exchange, stats_exchange, gstats_all=None,
-                    item_index_base=0, tail_stream=None, candidates_cap=None):
+                    item_index_base=0, candidates_cap=None):
     """Stages 0-1 of the int8 -> bf16 -> fp32 cascade (csrc/topk_cascade.hip): the [n_sb, n_users] table of superblock
     maxima whose entries are bf16 maxima wherever a top-k item can be and int8 maxima elsewhere (None after an overflow), its
     row stride, (resident rows of the bf16 launches, overflow), the k-th largest int8 lower bounds, and -- the default, DESIGN
@@ -628,8 +584,7 @@ def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, 
     the users (only the workgroup slots that hold rows are launched); rows kept by more are "hot" and re-scored for everybody
     by a dense launch.  When the int8 bound is too loose for the data -- more than CASCADE_MAX_REFINED of all pairs wanted --
     nothing is refined and the caller runs the dense bf16 stage 1 instead: the ONE host read of the call (three int64: rows,
-    overflow, hot rows) happens right after the compaction, before any bf16 launch.  ``tail_stream``: the refining launches
-    go there (ops._score_topk_filtered_pipelined)."""
+    overflow, hot rows) happens right after the compaction, before any bf16 launch."""
     dev = uop.bf16.device
     n_u, n_i, kpad = uop.n, iop.n, uop.kpad
     kk = int(k)
@@ -652,20 +607,18 @@ def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, 
     chunk_top = torch.empty((n_ch * top_k, stride), dtype=torch.float32, device=dev)
     lib = N.load()
     lists = cascade_lists_candidates() and gstats_all is not None and sb_rows <= 65536
-    one_pass = lib.trec_get_tuning(b"cascade_rows_onepass", 1) != 0 and lib.trec_get_tuning(b"blockmax_bf16_mfma16", 1) != 0
     # PRE-REFINEMENT (csrc/topk_filter.hip): the k superblocks with a user's k largest lower bounds are refined first and
     # tau rises to min(their bf16 maxima) - eps -- one e closer to the k-th best score, so the compaction keeps about half as many
     # pairs and the lists half as many candidates.  The chunk lists then carry the superblock's index inside its chunk in their low
     # bits.  Single process, candidate lists, catalogues the LDS counters cover; item shards keep the exchanged tau8.
     sb_per_chunk = chunk_len // sb_rows
-    pre = (one_pass and lists and floor_exchange is None and stats_exchange is None and kk <= WIDE_K_MAX
+    pre = (lists and floor_exchange is None and stats_exchange is None and kk <= WIDE_K_MAX
            and lib.trec_get_tuning(b"cascade_prerefine", 1) != 0 and sb_per_chunk <= 4096
            and CASCADE_PREREFINE_MIN_SB <= n_sb <= int(N.query("trec_topk_prerefine_max_superblocks")))
     if pre and kk > 16:
-        # the wide route (17 <= k <= 64): only in the default form -- the listing + marking launch and the threshold read back from
-        # its lists -- whose kernels take up to 64 slots per user (tuning wide_prerefine = 0: as before round 6, without)
-        pre = (lib.trec_get_tuning(b"cascade_prerefine", 1) == 1 and lib.trec_get_tuning(b"prerefine_marked", 1) != 0
-               and lib.trec_get_tuning(b"wide_prerefine", 1) != 0 and not _refine_resident(sb_rows, kpad)
+        # the wide route (17 <= k <= 64): the listing + marking launch and the threshold read back from its lists take up to 64
+        # slots per user (tuning wide_prerefine = 0: as before round 6, without)
+        pre = (lib.trec_get_tuning(b"wide_prerefine", 1) != 0
                and n_sb >= 4 * kk)                          # (k of n_sb superblocks per user: a small share of the pairs only then)
     with _timed("score_gemm_blockmax_i8"):
         N.call("trec_score_gemm_blockmax_i8", N.ptr(uop.i8), N.ptr(iop.i8), kpad, n_u, n_i, N.ptr(user_bias),
@@ -693,7 +646,7 @@ def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, 
     n_flagged0 = zb[6:7]
     row_count = zb[8:8 + n_sb]
     cands = None
-    if one_pass and lists:
+    if lists:
         # the refining launches also list every item that can still reach the top-k: provisional floor = the k-th
         # largest int8 lower bound less ONE eps of the bf16 filter.  ONE pass over the users (trec_topk_cascade_floor) makes the
         # thresholds: rows without a source keep nothing (tau = floor = +inf), users without a usable bound are flagged and
@@ -719,24 +672,21 @@ def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, 
             cands.items = torch.empty((n_u, cands.cap, 2), dtype=torch.int32, device=dev)
     if pre:
         # ---- the pre-refinement: lists of the users' k best superblocks, the bf16 launch over them, the sharper threshold.
-        # Default (tuning cascade_prerefine = 1): that launch also LISTS the candidates of those pairs (with the provisional floor
-        # tau8 - eps) and the pairs then leave the compaction's sight (table entry -inf, the bf16 maxima saved) -- nothing is refined
-        # twice.  cascade_prerefine = 2: maxima only, the entries marked +inf and refined again by the listing launch (A/B).
-        listed = 1 if lib.trec_get_tuning(b"cascade_prerefine", 1) == 1 else 0
+        # That launch also LISTS the candidates of those pairs (with the provisional floor tau8 - eps), keeps its maxima by list
+        # position and marks the table itself: the pairs leave the compaction's sight (table entry -inf, the bf16 maxima saved) --
+        # nothing is refined twice -- and the threshold kernel behind it reads a few tens of MB back instead of 10 random entries
+        # per user of the table
         n_cap_a = int(uop.n_real or n_u)
-        if listed:
-            # the compaction's own capacity (half of the users per superblock: on fitted / Zipf catalogues the k best superblocks of
-            # most users are the same few popular ones) -- only the workgroup slots that hold rows are launched (wg_map below)
-            rcap_frac_a = lib.trec_get_tuning(b"cascade_rcap_pct", int(100 * CASCADE_ROW_CAPACITY)) / 100.0
-            rcap_a = (int(rcap_frac_a * n_cap_a) + 511) // 512 * 512 + 512
-        else:
-            rcap_a = (2 * (n_cap_a * kk // n_sb + 1) + 1024 + 511) // 512 * 512
+        # the compaction's own capacity (half of the users per superblock: on fitted / Zipf catalogues the k best superblocks of
+        # most users are the same few popular ones) -- only the workgroup slots that hold rows are launched (wg_map below)
+        rcap_frac_a = lib.trec_get_tuning(b"cascade_rcap_pct", int(100 * CASCADE_ROW_CAPACITY)) / 100.0
+        rcap_a = (int(rcap_frac_a * n_cap_a) + 511) // 512 * 512 + 512
         pre_ws = zero_block(n_sb + 1, dev)                               # row counts of the pre-refining launch (+ one empty row: idle slots)
         sel_sb = torch.empty((n_u, kk), dtype=torch.int32, device=dev)
         pre_ok = torch.empty((n_u,), dtype=torch.int32, device=dev)
         pre_rows = torch.empty((n_sb * rcap_a,), dtype=torch.int32, device=dev)        # only the listed part is touched
-        pre_vals = torch.empty((n_u, kk), dtype=torch.float32, device=dev) if listed else None
-        if listed and n_sb >= 32 and lib.trec_get_tuning(b"prerefine_early_dense", 1 if kk <= 16 else 0) != 0:
+        pre_vals = torch.empty((n_u, kk), dtype=torch.float32, device=dev)
+        if n_sb >= 32 and lib.trec_get_tuning(b"prerefine_early_dense", 1 if kk <= 16 else 0) != 0:
             # users the int8 bound says nothing about (32 sampled superblocks under tau8) list nothing in the pre-refining launch
             # either: flagged now, as the call after the compaction would.  (The wide route leaves them to that later call: the
             # 64th largest lower bound keeps half of the sampled superblocks of a few users per 100,000 whom the RAISED threshold
@@ -744,179 +694,96 @@ def _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb, n_chunks, 
             N.call("trec_topk_dense_users", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err), N.ptr(iop.sb_stats),
                    kpad, CASCADE_DENSE_USER_LIMIT if n_i >= CASCADE_MIN_ITEMS else 30, N.ptr(cands.floor0), N.ptr(cands.flag),
                    N.ptr(cands.n_flagged))
-        resident_a = listed and _refine_resident(sb_rows, kpad)
-        # (default) the listing launch keeps its maxima by list position and marks the table itself: the threshold kernel behind it
-        # reads a few tens of MB back instead of 10 random entries per user of the table (tuning prerefine_marked = 0: the table pass)
-        marked = bool(listed) and not resident_a and lib.trec_get_tuning(b"prerefine_marked", 1) != 0
-        sel_pos = torch.empty((n_u, kk), dtype=torch.int32, device=dev) if marked else None
-        pre_max = torch.empty((n_sb * rcap_a,), dtype=torch.float32, device=dev) if marked else None       # only the listed part is touched
+        sel_pos = torch.empty((n_u, kk), dtype=torch.int32, device=dev)
+        pre_max = torch.empty((n_sb * rcap_a,), dtype=torch.float32, device=dev)       # only the listed part is touched
         with _timed("topk_prerefine"):
-            if marked:
-                N.call("trec_topk_prerefine_rows_pos", N.ptr(sel), N.ptr(sel_max), kk, top_k, sb_per_chunk, n_sb, n_u, N.ptr(uop.src),
-                       rcap_a, N.ptr(sel_sb), N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(pre_ok), N.ptr(sel_pos))
-            else:
-                N.call("trec_topk_prerefine_rows", N.ptr(sel), N.ptr(sel_max), kk, top_k, sb_per_chunk, n_sb, n_u, N.ptr(uop.src),
-                       rcap_a, N.ptr(sel_sb), N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(pre_ok))
-        if resident_a:
-            # the items of a superblock stay in registers, its user list streams through LDS in segments (csrc/refine_resident.hip)
-            seg_a, segs_a = _resident_segments(rcap_a)
-            n_wgs_a = n_cap_a * kk // seg_a + n_sb + 1
-            wg_start_a = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
-            wg_map_a = torch.full((n_wgs_a,), n_sb * segs_a, dtype=torch.int32, device=dev)
-            N.call("trec_topk_rows_wg_map_ex", N.ptr(pre_ws), n_sb, segs_a, seg_a, N.ptr(wg_start_a), N.ptr(wg_map_a), n_wgs_a)
-        elif listed:
-            # occupied workgroup slots only: at most pairs / 512 + one partial slot per superblock; the entries the map kernel does
-            # not reach point at the empty extra row
-            n_wgs_a = n_cap_a * kk // 512 + n_sb + 1
-            wg_start_a = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
-            wg_map_a = torch.full((n_wgs_a,), n_sb * (rcap_a // 512), dtype=torch.int32, device=dev)
-            N.call("trec_topk_rows_wg_map", N.ptr(pre_ws), n_sb, rcap_a // 512, N.ptr(wg_start_a), N.ptr(wg_map_a), n_wgs_a)
+            N.call("trec_topk_prerefine_rows_pos", N.ptr(sel), N.ptr(sel_max), kk, top_k, sb_per_chunk, n_sb, n_u, N.ptr(uop.src),
+                   rcap_a, N.ptr(sel_sb), N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(pre_ok), N.ptr(sel_pos))
+        # occupied workgroup slots only: at most pairs / 512 + one partial slot per superblock; the entries the map kernel does
+        # not reach point at the empty extra row
+        n_wgs_a = n_cap_a * kk // 512 + n_sb + 1
+        wg_start_a = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
+        wg_map_a = torch.full((n_wgs_a,), n_sb * (rcap_a // 512), dtype=torch.int32, device=dev)
+        N.call("trec_topk_rows_wg_map", N.ptr(pre_ws), n_sb, rcap_a // 512, N.ptr(wg_start_a), N.ptr(wg_map_a), n_wgs_a)
         with _timed("score_gemm_blockmax_pre"):
-            if resident_a:
-                N.call("trec_score_gemm_refine_candidates_resident", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, n_sb, N.ptr(pre_ws), N.ptr(pre_rows), rcap_a, N.ptr(table),
-                       stride, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
-                       N.ptr(wg_map_a), n_wgs_a, segs_a, seg_a)
-            elif marked:
-                N.call("trec_score_gemm_refine_candidates_marked", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap_a, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(table), stride,
-                       rcap_a // 512, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
-                       N.ptr(wg_map_a), n_wgs_a, N.ptr(pre_max))
-            elif listed:
-                N.call("trec_score_gemm_refine_candidates", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap_a, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(table), stride,
-                       rcap_a // 512, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
-                       N.ptr(wg_map_a), n_wgs_a)
-            else:
-                N.call("trec_score_gemm_blockmax_grouped", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap_a, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(table), stride,
-                       rcap_a // 512)
+            N.call("trec_score_gemm_refine_candidates_marked", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap_a, n_i,
+                   N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(pre_ws), N.ptr(pre_rows), N.ptr(table), stride,
+                   rcap_a // 512, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
+                   N.ptr(wg_map_a), n_wgs_a, N.ptr(pre_max))
         with _timed("topk_prerefine"):
-            if marked:
-                N.call("trec_topk_prerefine_tau_listed", N.ptr(sel_sb), N.ptr(sel_pos), N.ptr(pre_ok), kk, N.ptr(pre_max), rcap_a, n_u,
-                       N.ptr(uop.src), N.ptr(uop.stats), N.ptr(user_bias), N.ptr(gstats_all), kpad, N.ptr(tau), N.ptr(pre_vals),
-                       N.ptr(cands.floor0))
-            else:
-                N.call("trec_topk_prerefine_tau", N.ptr(sel_sb), N.ptr(pre_ok), kk, N.ptr(table), stride, n_u, N.ptr(uop.src),
-                       N.ptr(uop.stats), N.ptr(user_bias), N.ptr(gstats_all), kpad, N.ptr(tau), listed, N.ptr(pre_vals),
-                       N.ptr(cands.floor0))
-        if listed:
-            cands.pre = (sel_sb, pre_vals)          # (the saved maxima go back into the columns of users re-done from the table)
+            N.call("trec_topk_prerefine_tau_listed", N.ptr(sel_sb), N.ptr(sel_pos), N.ptr(pre_ok), kk, N.ptr(pre_max), rcap_a, n_u,
+                   N.ptr(uop.src), N.ptr(uop.stats), N.ptr(user_bias), N.ptr(gstats_all), kpad, N.ptr(tau), N.ptr(pre_vals),
+                   N.ptr(cands.floor0))
+        cands.pre = (sel_sb, pre_vals)              # (the saved maxima go back into the columns of users re-done from the table)
         if FILTER_DEBUG is not None:
             FILTER_DEBUG.update({"prerefine_users_ok": int(pre_ok.sum().item()), "prerefine_rcap": rcap_a,
-                                 "prerefine_row_count_max": int(pre_ws[:n_sb].max().item()), "prerefine_listed": listed,
+                                 "prerefine_row_count_max": int(pre_ws[:n_sb].max().item()), "prerefine_listed": 1,
                                  "prerefine_pairs": int((sel_sb >= 0).sum().item())})
     if cands is None and uop.src is not None:
         tau.masked_fill_(uop.src < 0, float("inf"))     # rows without a source refine nothing (the table-driven tail: A/B reference)
-    if one_pass:
-        # one pass over the table: a fixed capacity per superblock, slots handed out by atomics (csrc/topk_cascade.hip)
-        # (capacities are fractions of the REAL users: a class-sorted layout of few users is mostly rows without a source)
-        n_cap = int(uop.n_real or n_u)
-        rcap_frac = N.load().trec_get_tuning(b"cascade_rcap_pct", int(100 * CASCADE_ROW_CAPACITY)) / 100.0
-        rcap = (int(rcap_frac * n_cap) + 511) // 512 * 512 + 512
-        row_user = torch.empty((n_sb * rcap,), dtype=torch.int32, device=dev)      # only the kept pairs' part is touched
-        with _timed("topk_rows_compact"):
-            N.call("trec_topk_rows_collect", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err),
-                   N.ptr(iop.sb_stats), kpad, rcap, N.ptr(row_count), N.ptr(row_user), N.ptr(status))
-        if FILTER_DEBUG is not None:
-            FILTER_DEBUG.update({"int8_pairs_wanted": int(row_count.sum().item()), "int8_pairs_total": int(n_sb) * int(n_u),
-                                 "rcap": rcap, "row_count_max": int(row_count.max().item()),
-                                 "hot_superblocks": int((row_count > rcap).sum().item())})
-        # "hot" superblocks -- kept by more users than rcap: the few rows that hold a skewed catalogue's most popular items --
-        # are refined for EVERY user by a dense launch over that list; the fixed-capacity launch skips them
-        hot_cap = max(8, min(N.load().trec_get_tuning(b"cascade_max_hot", CASCADE_MAX_HOT), n_sb))
-        hot_list = torch.empty((hot_cap,), dtype=torch.int32, device=dev)
-        max_pairs = int(N.load().trec_get_tuning(b"cascade_max_refined_pct", int(100 * CASCADE_MAX_REFINED)) / 100.0 * n_sb * n_cap)
-        N.call("trec_topk_rows_hot", N.ptr(row_count), n_sb, rcap, n_u, N.ptr(hot_list), hot_cap, max_pairs, N.ptr(status))
-        # Everything that does not need the host's decision is queued BEFORE the host reads the status -- behind the int8 launch,
-        # while it still runs: the thresholds above, the users the int8 bound says nothing about, the map of the occupied
-        # workgroup slots.  After the read only the refining launches and the finish remain.
-        wg_map, wg_cap = None, 0
-        if cands is not None:
-            if n_sb >= 32:                              # users the int8 bound says nothing about are flagged now, not listed for
-                N.call("trec_topk_dense_users", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err), N.ptr(iop.sb_stats),
-                       kpad, CASCADE_DENSE_USER_LIMIT if n_i >= CASCADE_MIN_ITEMS else 30, N.ptr(cands.floor0), N.ptr(cands.flag),
-                       N.ptr(cands.n_flagged))             # (small catalogues: the k-th largest of few maxima keeps half the rows of anybody)
-            resident = _refine_resident(sb_rows, kpad)
-            if resident:
-                # the items of a superblock resident, its user list in segments (csrc/refine_resident.hip): the map lists the
-                # occupied (superblock, segment) slots; the rest of its entries stay idle
-                seg_r, segs_r = _resident_segments(rcap)
-                wg_cap = min(n_sb * segs_r, max_pairs // seg_r + n_sb + 1)
-                wg_start = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
-                wg_map = torch.full((wg_cap,), n_sb * segs_r, dtype=torch.int32, device=dev)
-                N.call("trec_topk_rows_wg_map_ex", N.ptr(row_count), n_sb, segs_r, seg_r, N.ptr(wg_start), N.ptr(wg_map), wg_cap)
-            elif N.load().trec_get_tuning(b"cascade_wg_map", 1) != 0:
-                # only the workgroup slots that hold rows are launched (98k of the 1.9M of the [n_sb][rcap / 512] grid at 1M x 1M)
-                wg_cap = min(n_sb * (rcap // 512), max_pairs // 512 + n_sb + 1)
-                wg_start = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
-                wg_map = torch.empty((wg_cap,), dtype=torch.int32, device=dev)
-                N.call("trec_topk_rows_wg_map", N.ptr(row_count), n_sb, rcap // 512, N.ptr(wg_start), N.ptr(wg_map), wg_cap)
-        # the overflow flag is read HERE, before the bf16 launches: when the int8 bound is too loose, refining
-        # close to half of all pairs and then running the filter's tail on the result would only be thrown away.  One host
-        # read per call; item shards agree on it (MAX).
-        rows, overflow, n_hot = status.tolist()
-        if stats_exchange is not None:
-            overflow = float(stats_exchange(torch.tensor([float(overflow)], device=dev)).item())
-        if overflow:
-            return None, stride, (int(rows), True), tau, None
-        n_hot = min(int(n_hot), hot_cap)                # the hot launch's grid: nothing is launched when no superblock is hot
-        n_wgs = 0
-        if wg_map is not None and cands is not None and resident:
-            n_wgs = min(wg_cap, (int(rows) - n_hot * ((n_u + 511) // 512 * 512)) // seg_r + n_sb + 1)
-        elif wg_map is not None:
-            n_wgs = min(wg_cap, (int(rows) - n_hot * ((n_u + 511) // 512 * 512)) // 512)
-        # (user batches in a pipeline: from here on the launches go to the tail stream, next to the following batch's int8 stage)
-        tail = _tail_of(tail_stream if cands is not None else None, table, row_count, row_user, hot_list, wg_map,
-                        *((cands.floor0, cands.n, cands.items) if cands is not None else ()))
-        with tail, _timed("score_gemm_blockmax_grouped"):
-            if cands is not None and resident:
-                N.call("trec_score_gemm_refine_candidates_resident", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, n_sb, N.ptr(row_count), N.ptr(row_user), rcap, N.ptr(table),
-                       stride, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
-                       N.ptr(wg_map), n_wgs, segs_r, seg_r)
-            elif cands is not None:
-                N.call("trec_score_gemm_refine_candidates", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(row_count), N.ptr(row_user), N.ptr(table), stride,
-                       rcap // 512, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
-                       N.ptr(wg_map), n_wgs)
-            else:
-                N.call("trec_score_gemm_blockmax_grouped", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(row_count), N.ptr(row_user), N.ptr(table), stride,
-                       rcap // 512)
-        with _tail_of(tail_stream if cands is not None else None), _timed("score_gemm_blockmax_hot"):
-            if n_hot == 0:
-                pass
-            elif cands is not None:
-                N.call("trec_score_gemm_refine_candidates_hot", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_u, n_i,
-                       N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(hot_list), n_hot, N.ptr(table), stride,
-                       N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base))
-            else:
-                N.call("trec_score_gemm_blockmax_hot", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_u, n_i, N.ptr(user_bias),
-                       N.ptr(item_bias), sb_rows, N.ptr(hot_list), n_hot, N.ptr(table), stride)
-        return table, stride, (int(rows), False), tau, cands
-    n_ublk = N.query("trec_topk_rows_user_blocks", n_u)
-    block_off = torch.empty((n_sb * n_ublk,), dtype=torch.int32, device=dev)
-    row_total = torch.empty((n_sb,), dtype=torch.int32, device=dev)
-    row_pad = torch.empty((n_sb,), dtype=torch.int32, device=dev)
-    pstart = torch.empty((n_sb + 1,), dtype=torch.int64, device=dev)
-    cap_rows = (int(CASCADE_MAX_REFINED * n_sb * n_u) + 511) // 512 * 512 + 512 * n_sb
-    row_user = torch.empty((cap_rows,), dtype=torch.int32, device=dev)          # only the kept pairs' part is touched
-    rblock_chunk = torch.empty((cap_rows // 512,), dtype=torch.int32, device=dev)
+    # one pass over the table: a fixed capacity per superblock, slots handed out by atomics (csrc/topk_cascade.hip)
+    # (capacities are fractions of the REAL users: a class-sorted layout of few users is mostly rows without a source)
+    n_cap = int(uop.n_real or n_u)
+    rcap_frac = N.load().trec_get_tuning(b"cascade_rcap_pct", int(100 * CASCADE_ROW_CAPACITY)) / 100.0
+    rcap = (int(rcap_frac * n_cap) + 511) // 512 * 512 + 512
+    row_user = torch.empty((n_sb * rcap,), dtype=torch.int32, device=dev)      # only the kept pairs' part is touched
     with _timed("topk_rows_compact"):
-        N.call("trec_topk_rows_count", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err), N.ptr(iop.sb_stats),
-               kpad, N.ptr(block_off), N.ptr(row_total), N.ptr(row_pad), N.ptr(pstart), cap_rows, N.ptr(status))
-        N.call("trec_topk_rows_fill", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err), N.ptr(iop.sb_stats),
-               kpad, N.ptr(block_off), N.ptr(row_total), N.ptr(pstart), cap_rows, N.ptr(status), N.ptr(row_user),
-               N.ptr(rblock_chunk))
-    with _timed("score_gemm_blockmax_grouped"):
-        N.call("trec_score_gemm_blockmax_grouped", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, cap_rows, n_i,
-               N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(rblock_chunk), N.ptr(row_user), N.ptr(table), stride, 0)
-    rows, overflow = status.tolist()[:2]                # (the two-pass form: its fill pass and grouped launch idle after an overflow)
+        N.call("trec_topk_rows_collect", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err),
+               N.ptr(iop.sb_stats), kpad, rcap, N.ptr(row_count), N.ptr(row_user), N.ptr(status))
+    if FILTER_DEBUG is not None:
+        FILTER_DEBUG.update({"int8_pairs_wanted": int(row_count.sum().item()), "int8_pairs_total": int(n_sb) * int(n_u),
+                             "rcap": rcap, "row_count_max": int(row_count.max().item()),
+                             "hot_superblocks": int((row_count > rcap).sum().item())})
+    # "hot" superblocks -- kept by more users than rcap: the few rows that hold a skewed catalogue's most popular items --
+    # are refined for EVERY user by a dense launch over that list; the fixed-capacity launch skips them
+    hot_cap = max(8, min(N.load().trec_get_tuning(b"cascade_max_hot", CASCADE_MAX_HOT), n_sb))
+    hot_list = torch.empty((hot_cap,), dtype=torch.int32, device=dev)
+    max_pairs = int(N.load().trec_get_tuning(b"cascade_max_refined_pct", int(100 * CASCADE_MAX_REFINED)) / 100.0 * n_sb * n_cap)
+    N.call("trec_topk_rows_hot", N.ptr(row_count), n_sb, rcap, n_u, N.ptr(hot_list), hot_cap, max_pairs, N.ptr(status))
+    # Everything that does not need the host's decision is queued BEFORE the host reads the status -- behind the int8 launch,
+    # while it still runs: the thresholds above, the users the int8 bound says nothing about, the map of the occupied
+    # workgroup slots.  After the read only the refining launches and the finish remain.
+    if cands is not None:
+        if n_sb >= 32:                              # users the int8 bound says nothing about are flagged now, not listed for
+            N.call("trec_topk_dense_users", N.ptr(table), n_sb, n_u, stride, N.ptr(tau), N.ptr(user_err), N.ptr(iop.sb_stats),
+                   kpad, CASCADE_DENSE_USER_LIMIT if n_i >= CASCADE_MIN_ITEMS else 30, N.ptr(cands.floor0), N.ptr(cands.flag),
+                   N.ptr(cands.n_flagged))             # (small catalogues: the k-th largest of few maxima keeps half the rows of anybody)
+        # only the workgroup slots that hold rows are launched (98k of the 1.9M of the [n_sb][rcap / 512] grid at 1M x 1M)
+        wg_cap = min(n_sb * (rcap // 512), max_pairs // 512 + n_sb + 1)
+        wg_start = torch.empty((n_sb + 1,), dtype=torch.int32, device=dev)
+        wg_map = torch.empty((wg_cap,), dtype=torch.int32, device=dev)
+        N.call("trec_topk_rows_wg_map", N.ptr(row_count), n_sb, rcap // 512, N.ptr(wg_start), N.ptr(wg_map), wg_cap)
+    # the overflow flag is read HERE, before the bf16 launches: when the int8 bound is too loose, refining
+    # close to half of all pairs and then running the filter's tail on the result would only be thrown away.  One host
+    # read per call; item shards agree on it (MAX).
+    rows, overflow, n_hot = status.tolist()
     if stats_exchange is not None:
         overflow = float(stats_exchange(torch.tensor([float(overflow)], device=dev)).item())
-    return (None if overflow else table), stride, (int(rows), bool(overflow)), tau, None
-
+    if overflow:
+        return None, stride, (int(rows), True), tau, None
+    n_hot = min(int(n_hot), hot_cap)                # the hot launch's grid: nothing is launched when no superblock is hot
+    with _timed("score_gemm_blockmax_grouped"):
+        if cands is not None:
+            n_wgs = min(wg_cap, (int(rows) - n_hot * ((n_u + 511) // 512 * 512)) // 512)
+            N.call("trec_score_gemm_refine_candidates", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap, n_i,
+                   N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(row_count), N.ptr(row_user), N.ptr(table), stride,
+                   rcap // 512, N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base),
+                   N.ptr(wg_map), n_wgs)
+        else:
+            N.call("trec_score_gemm_blockmax_grouped", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_sb * rcap, n_i,
+                   N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(row_count), N.ptr(row_user), N.ptr(table), stride,
+                   rcap // 512)
+    with _timed("score_gemm_blockmax_hot"):
+        if n_hot == 0:
+            pass
+        elif cands is not None:
+            N.call("trec_score_gemm_refine_candidates_hot", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_u, n_i,
+                   N.ptr(user_bias), N.ptr(item_bias), sb_rows, N.ptr(hot_list), n_hot, N.ptr(table), stride,
+                   N.ptr(cands.floor0), N.ptr(cands.n), N.ptr(cands.items), cands.cap, int(item_index_base))
+        else:
+            N.call("trec_score_gemm_blockmax_hot", N.ptr(uop.bf16), N.ptr(iop.bf16), kpad, n_u, n_i, N.ptr(user_bias),
+                   N.ptr(item_bias), sb_rows, N.ptr(hot_list), n_hot, N.ptr(table), stride)
+    return table, stride, (int(rows), False), tau, cands
 
 def _filter_tail(uop, iop, blockmax, bm_stride, n_u, n_sb, k, user_bias, item_bias, item_index_base, sb_rows, variant, ksel,
                  cap, floor, flag, n_flagged, rows_wg, wide=False, keys_count=None):
@@ -1033,104 +900,15 @@ def score_topk_filtered(uop, iop, k, user_bias=None, item_bias=None, item_index_
         ub = uop.bias_sorted
     else:
         ub = user_bias.reshape(-1).index_select(0, uop.perm).masked_fill_(uop.pad, 0.0)
-    n_batches = cascade_user_batches(uop, iop, prefilter, floor_exchange, stats_exchange)
-    if n_batches > 1:
-        sv, si = _score_topk_filtered_pipelined(uop, iop, k, ub, item_bias, item_index_base, sb_rows, variant, n_chunks, ksel,
-                                                n_batches)
-        pos = uop.pos.long()
-        ov, oi = sv.index_select(0, pos), si.index_select(0, pos)
-    else:
-        ov, oi = _score_topk_filtered(uop, iop, k, ub, item_bias, item_index_base, sb_rows, variant, n_chunks,
-                                      floor_exchange, stats_exchange, ksel, prefilter, caller_order=True, finish_lanes=finish_lanes)
+    ov, oi = _score_topk_filtered(uop, iop, k, ub, item_bias, item_index_base, sb_rows, variant, n_chunks,
+                                  floor_exchange, stats_exchange, ksel, prefilter, caller_order=True, finish_lanes=finish_lanes)
     LAST_FILTER_STATS["users"] = int(uop.n_real)
     LAST_FILTER_STATS["layout_rows"] = int(uop.n)
     return ov, oi
 
 
-CASCADE_PIPELINE_MIN_ROWS = 131072     # user rows per batch below which the two-stream pipeline is not worth its launches
-_TAIL_STREAMS = {}
-
-
-def cascade_user_batches(uop, iop, prefilter, floor_exchange, stats_exchange):
-    """User batches of the two-stream pipeline (tuning ``cascade_user_batches``; default 1 = off): the int8 stage of batch
-    b + 1 runs next to the bf16 refinement and the finish of batch b -- the first is bound by the matrix pipe at the power limit,
-    the others by gathers and latencies.  Single process, class-sorted users, a catalogue the cascade is used on.
-    MEASURED at 1M x 1M: 4 batches 98.6-98.8 ms against 95.7-96.5 for one -- the tail kernels do run next to the
-    int8 launch (their event time stretches to its ~20 ms) but the chip is at its power limit either way: the int8 launches
-    lose what the hidden tail gains, and four smaller launches of everything cost more than one.  Kept as a knob."""
-    want = N.load().trec_get_tuning(b"cascade_user_batches", 1)
-    if want <= 1 or prefilter != "int8" or floor_exchange is not None or stats_exchange is not None or uop.wg_rows is None:
-        return 1
-    if uop.kpad not in (64, 128) or iop.cascade_too_loose or not cascade_lists_candidates():
-        return 1
-    return max(1, min(int(want), int(uop.n_real or uop.n) // CASCADE_PIPELINE_MIN_ROWS))
-
-
-def _rows_of(uop, r0, r1):
-    """Rows r0 .. r1 (multiples of the int8 workgroup height) of a class-sorted user operand, as views."""
-    sub = FilterOperand()
-    sub.n, sub.n_real, sub.d, sub.kpad = r1 - r0, r1 - r0, uop.d, uop.kpad
-    sub.bf16, sub.f32, sub.stats = uop.bf16[r0:r1], uop.f32[r0:r1], uop.stats[r0:r1]
-    sub.i8, sub.stats8 = uop.i8[r0:r1], uop.stats8[r0:r1]
-    sub.src = uop.src[r0:r1]
-    sub.wg_rows = uop.wg_rows
-    sub.wg_scale = uop.wg_scale[r0 // uop.wg_rows:r1 // uop.wg_rows]
-    sub.wg_class = uop.wg_class[r0 // uop.wg_rows:r1 // uop.wg_rows]
-    sub.gmax, sub.ladder, sub.class_used = uop.gmax, uop.ladder, uop.class_used
-    return sub
-
-
-def _score_topk_filtered_pipelined(uop, iop, k, user_bias, item_bias, item_index_base, sb_rows, variant, n_chunks, ksel, n_batches):
-    """_score_topk_filtered(prefilter="int8") over ``n_batches`` row ranges of the class-sorted operand, two streams: everything
-    up to the host's read of the compaction status runs on the caller's stream, the bf16 refinement and the finish of a batch on
-    a second one -- next to the following batch's int8 stage.  The flagged users of all batches are re-done at the end."""
-    sb_rows = int(sb_rows or SUPERBLOCK_ROWS)
-    top_k = 10 if int(k) <= 10 else 16
-    if uop.i8 is None or iop.i8 is None or iop.sb_rows != sb_rows or iop.bias_owner is None or iop.bias_owner() is not uop:
-        score_prep_i8_pair(uop, iop, item_bias, sb_rows, top_k)          # ONCE for all batches (the classes in use, the item biases)
-    dev = uop.bf16.device
-    main = torch.cuda.current_stream()
-    tail = _TAIL_STREAMS.get(dev)
-    if tail is None:
-        # high priority: a tail kernel's workgroups take the slots the int8 kernel's retiring workgroups free (at equal priority
-        # the int8 launch -- queued first, 16,000+ workgroups -- keeps every slot and the tail only runs once it has drained)
-        prio = -1 if N.load().trec_get_tuning(b"cascade_tail_priority", 1) != 0 else 0
-        tail = _TAIL_STREAMS[dev] = torch.cuda.Stream(device=dev, priority=prio)
-    wgs = int(uop.n) // int(uop.wg_rows)
-    bounds = [int(uop.wg_rows) * (wgs * b // n_batches) for b in range(n_batches + 1)]
-    parts = []
-    for b in range(n_batches):
-        r0, r1 = bounds[b], bounds[b + 1]
-        sub = _rows_of(uop, r0, r1)
-        iop.bias_owner = __import__("weakref").ref(sub)         # (the tables made for the whole operand serve its row ranges)
-        ub = user_bias[r0:r1] if user_bias is not None else None
-        parts.append(_score_topk_filtered(sub, iop, k, ub, item_bias, item_index_base, sb_rows, variant, n_chunks, None, None,
-                                          ksel, "int8", tail_stream=tail))
-        if not isinstance(parts[-1], _Pending):
-            parts[-1] = (parts[-1], dict(LAST_FILTER_STATS))
-    main.wait_stream(tail)
-    out_v, out_i, stats = [], [], []
-    for part in parts:
-        if isinstance(part, _Pending):
-            v, i = part.complete()
-            part = ((v, i), dict(LAST_FILTER_STATS))
-        out_v.append(part[0][0]); out_i.append(part[0][1]); stats.append(part[1])
-    LAST_FILTER_STATS.clear()
-    LAST_FILTER_STATS.update(stats[0])
-    for key in ("refined_rows", "users", "flagged_users", "flagged_after_wide_pass", "flagged_after_wide_pass_2",
-                "users_on_fp32_fallback"):
-        if any(key in st for st in stats):
-            LAST_FILTER_STATS[key] = sum(st.get(key, 0) for st in stats)
-    if all("candidates_per_user" in st for st in stats):
-        LAST_FILTER_STATS["candidates_per_user"] = sum(st["candidates_per_user"] * st["users"] for st in stats) / max(1, uop.n)
-    if any(st.get("prefilter") != "int8" for st in stats):
-        LAST_FILTER_STATS["prefilter"] = "; ".join(sorted(set(str(st.get("prefilter")) for st in stats)))
-    LAST_FILTER_STATS["user_batches"] = n_batches
-    return torch.cat(out_v), torch.cat(out_i)
-
-
 def _score_topk_filtered(uop, iop, k, user_bias=None, item_bias=None, item_index_base=0, sb_rows=None, variant=1,
-                         n_chunks=None, floor_exchange=None, stats_exchange=None, ksel=None, prefilter=None, tail_stream=None,
+                         n_chunks=None, floor_exchange=None, stats_exchange=None, ksel=None, prefilter=None,
                          caller_order=False, finish_lanes=0):
     """EXACT fp32 top-k (values and ids bit-identical to ``score_topk(..., DTYPE_F32)`` and to the oracle) with the
     score matrix contracted ONCE on bf16 MFMA: the bf16 stage-1 maxima and the bf16 re-scoring act as a filter with a
@@ -1172,7 +950,7 @@ def _score_topk_filtered(uop, iop, k, user_bias=None, item_bias=None, item_index
         # ---- stages 0 + 1: int8 maxima everywhere, bf16 maxima where a top-k item can be
         blockmax, bm_stride, cascade_status, tau8, cands = _cascade_stage1(uop, iop, k, user_bias, item_bias, sb_rows, n_sb,
                                                                            n_chunks, floor_exchange, stats_exchange, gstats,
-                                                                           item_index_base, tail_stream)
+                                                                           item_index_base)
         rows, overflow = cascade_status
         if overflow:
             # the int8 bound was too loose for this data: nothing was refined.  bf16 does stage 1; the next user batches
@@ -1212,9 +990,9 @@ def _score_topk_filtered(uop, iop, k, user_bias=None, item_bias=None, item_index
         # per user, four users per wave, and the wave-per-user form only for the users beyond 64 entries (tuning finish_mixed: 0 =
         # a wave per user for everybody, the A/B reference; 1 / 2 / 4 = candidates per lane)
         mixed = int(N.load().trec_get_tuning(b"finish_mixed", 4)) if not finish_lanes and cands.cap <= 256 else 0
-        with _tail_of(tail_stream, ov, oi, flag, n_flagged, gstats), _timed("topk_filter_finish"):
+        with _timed("topk_filter_finish"):
             if mixed in (1, 2, 4):
-                over_count = zero_block(2, dev)             # (allocated inside the tail-stream context: they live on the stream they are used on)
+                over_count = zero_block(2, dev)
                 over_list = torch.empty((n_u,), dtype=torch.int32, device=dev)
                 N.call("trec_topk_candidates_finish_mixed", N.ptr(cands.n), N.ptr(cands.items), cands.cap, N.ptr(cands.floor0),
                        N.ptr(uop.stats), N.ptr(gstats), N.ptr(uop.f32), N.ptr(iop.f32), kpad, kpad, uop.d, N.ptr(user_bias),
@@ -1226,33 +1004,27 @@ def _score_topk_filtered(uop, iop, k, user_bias=None, item_bias=None, item_index
                        N.ptr(item_bias), item_index_base, n_u, kk, N.ptr(ov), N.ptr(oi), N.ptr(flag), N.ptr(n_flagged),
                        N.ptr(out_index), int(finish_lanes or 0))
 
-        def complete(cands=cands, blockmax=blockmax):
-            if FILTER_DEBUG is not None:
-                _debug_counts("candidates", cands.n)
-            # ONE host read: the flagged-user counter (queued behind the finish kernel)
-            n_bad = int(n_flagged.item())
-            if n_bad and cands.pre is not None:
-                # the pre-refined pairs of the users to re-do: their bf16 maxima return to the table (the compaction saw -inf there)
-                sel_sb, pre_vals = cands.pre
-                bad_u = torch.nonzero(flag, as_tuple=False).reshape(-1)
-                sb_b = sel_sb.index_select(0, bad_u).long()
-                hit = sb_b >= 0
-                blockmax[sb_b[hit], bad_u.reshape(-1, 1).expand_as(sb_b)[hit]] = pre_vals.index_select(0, bad_u)[hit]
-            LAST_FILTER_STATS.clear()
-            LAST_FILTER_STATS.update({"prefilter": "int8", "refined_rows": cascade_rows, "users": n_u, "flagged_users": n_bad,
-                                      "tail": "candidate lists", "candidates_cap": cands.cap})
-            if cands.pre is not None:
-                # (at most: a slot whose superblock list was full stays with the compaction)
-                LAST_FILTER_STATS["prerefined_pairs"] = int(uop.n_real or n_u) * int(k)
-            if CANDIDATE_STATS:                           # diagnostics (a reduction over the counters + a host read): off the product path
-                LAST_FILTER_STATS["candidates_per_user"] = float(cands.n.clamp(max=cands.cap).sum().item()) / \
-                    max(1, int(uop.n_real or n_u))        # (per real user: the layout's rows without a source list nothing)
-            return _redo_flagged(uop, iop, blockmax, flag, n_bad, n_sb, k, user_bias, item_bias, item_index_base, sb_rows,
-                                 variant, None, rows_wg, ksel, gstats, ov, oi, out_index)
-        cands = blockmax = None
-        if tail_stream is not None:
-            return _Pending(complete)
-        return complete()
+        if FILTER_DEBUG is not None:
+            _debug_counts("candidates", cands.n)
+        # ONE host read: the flagged-user counter (queued behind the finish kernel)
+        n_bad = int(n_flagged.item())
+        if n_bad and cands.pre is not None:
+            # the pre-refined pairs of the users to re-do: their bf16 maxima return to the table (the compaction saw -inf there)
+            sel_sb, pre_vals = cands.pre
+            bad_u = torch.nonzero(flag, as_tuple=False).reshape(-1)
+            sb_b = sel_sb.index_select(0, bad_u).long()
+            hit = sb_b >= 0
+            blockmax[sb_b[hit], bad_u.reshape(-1, 1).expand_as(sb_b)[hit]] = pre_vals.index_select(0, bad_u)[hit]
+        LAST_FILTER_STATS.update({"prefilter": "int8", "refined_rows": cascade_rows, "users": n_u, "flagged_users": n_bad,
+                                  "tail": "candidate lists", "candidates_cap": cands.cap})
+        if cands.pre is not None:
+            # (at most: a slot whose superblock list was full stays with the compaction)
+            LAST_FILTER_STATS["prerefined_pairs"] = int(uop.n_real or n_u) * int(k)
+        if CANDIDATE_STATS:                           # diagnostics (a reduction over the counters + a host read): off the product path
+            LAST_FILTER_STATS["candidates_per_user"] = float(cands.n.clamp(max=cands.cap).sum().item()) / \
+                max(1, int(uop.n_real or n_u))        # (per real user: the layout's rows without a source list nothing)
+        return _redo_flagged(uop, iop, blockmax, flag, n_bad, n_sb, k, user_bias, item_bias, item_index_base, sb_rows,
+                             variant, None, rows_wg, ksel, gstats, ov, oi, out_index)
     tau = torch.empty((n_u,), dtype=torch.float32, device=dev)
     sel_max = torch.empty((kk, n_u), dtype=torch.float32, device=dev) if floor_exchange is not None else None
     floor = torch.empty((n_u,), dtype=torch.float32, device=dev)

@@ -297,23 +297,21 @@ def test_int8_bound_is_tight_but_holds_on_aligned_quantisation_errors(ops):
     assert np.median(at_partner) > 0.6                                        # coherent errors use most of the bound
 
 
-def test_rows_compaction_lists_exactly_the_pairs_whose_upper_bound_reaches_the_threshold(ops):
+def test_rows_collect_one_pass_keeps_the_same_pairs(ops):
+    """trec_topk_rows_collect: per superblock exactly the SET of users whose upper bound reaches their threshold (the order
+    follows the atomics), the counts, the overflow flag when a superblock keeps more than the capacity.  A threshold of +inf
+    keeps nothing; a superblock with an unusable bound is kept by everybody else (the last shape, where it fits the capacity)."""
     from tensorrec_amd import _native as N
-    rng = np.random.default_rng(2)
-    for n_sb, n_u, stride in ((37, 5000, 5000), (9, 1023, 1024), (130, 2050, 2051)):
+    rng = np.random.default_rng(12)
+    for n_sb, n_u, stride, rcap in ((37, 5000, 5000, 2048), (130, 2050, 2051, 1024), (9, 3000, 3000, 512), (9, 1023, 1024, 1024)):
         table = rng.standard_normal((n_sb, stride)).astype(np.float32)
         thr = rng.uniform(0.5, 2.5, n_u).astype(np.float32)
         thr[5] = -np.inf                                                       # a user that keeps every superblock
         thr[6] = np.inf
         uerr = rng.uniform(0.0, 0.3, (n_u, 4)).astype(np.float32)              # {||x||, ||x - a q||, cu, a}
         sbs = rng.uniform(0.0, 1.0, (n_sb, 4)).astype(np.float32)
-        sbs[3, 2] = np.inf                                                     # a superblock with an unusable bound: always kept
-        dt, dth, due, dsb = dev(table), dev(thr), dev(uerr), dev(sbs)
-        n_ublk = N.query("trec_topk_rows_user_blocks", n_u)
-        block_off = torch.empty((n_sb * n_ublk,), dtype=torch.int32, device="cuda")
-        row_total = torch.empty((n_sb,), dtype=torch.int32, device="cuda")
-        row_pad = torch.empty((n_sb,), dtype=torch.int32, device="cuda")
-        pstart = torch.empty((n_sb + 1,), dtype=torch.int64, device="cuda")
+        if rcap >= n_u:
+            sbs[3, 2] = np.inf                                                 # a superblock with an unusable bound: always kept
         with np.errstate(invalid="ignore", over="ignore"):
             # tile_bits (csrc/topk_cascade.hip), operation for operation in float32 (fma through float64: exact product)
             f32, f64 = np.float32, np.float64
@@ -335,62 +333,9 @@ def test_rows_compaction_lists_exactly_the_pairs_whose_upper_bound_reaches_the_t
                           fma(np.broadcast_to(uerr[:, 3][None, :], tv.shape), np.broadcast_to(C, tv.shape), tv)))
             keep = ~(lhs < f[None, :])
             keep[:, ~(thr < np.inf)] = False          # a threshold of +inf keeps NOTHING, whatever the table or the bound holds
-        want_rows = int(((keep.sum(1) + 511) // 512 * 512).sum())
-        for cap_rows in (want_rows + 1024, want_rows, want_rows - 512):          # roomy, exact fit, one workgroup short
-            status = torch.full((2,), -5, dtype=torch.int64, device="cuda")
-            N.call("trec_topk_rows_count", N.ptr(dt), n_sb, n_u, stride, N.ptr(dth), N.ptr(due), N.ptr(dsb), 128,
-                   N.ptr(block_off), N.ptr(row_total), N.ptr(row_pad), N.ptr(pstart), cap_rows, N.ptr(status))
-            assert np.array_equal(row_total.cpu().numpy(), keep.sum(1))
-            ps = pstart.cpu().numpy()
-            assert np.array_equal(np.diff(ps), (keep.sum(1) + 511) // 512 * 512)
-            assert status.tolist() == [want_rows, int(want_rows > cap_rows)]
-            row_user = torch.full((cap_rows,), -7, dtype=torch.int32, device="cuda")
-            rblock_chunk = torch.full((cap_rows // 512,), -7, dtype=torch.int32, device="cuda")
-            N.call("trec_topk_rows_fill", N.ptr(dt), n_sb, n_u, stride, N.ptr(dth), N.ptr(due), N.ptr(dsb), 128,
-                   N.ptr(block_off), N.ptr(row_total), N.ptr(pstart), cap_rows, N.ptr(status), N.ptr(row_user),
-                   N.ptr(rblock_chunk))
-            ru, rc = row_user.cpu().numpy(), rblock_chunk.cpu().numpy()
-            if want_rows > cap_rows:                                              # overflow: every workgroup idle, no row written
-                assert np.all(rc == -1) and np.all(ru == -7)
-                continue
-            for s in range(n_sb):
-                users = np.nonzero(keep[s])[0]
-                seg = ru[ps[s]:ps[s + 1]]
-                assert np.array_equal(seg[:len(users)], users) and np.all(seg[len(users):] == -1)
-                assert np.all(rc[ps[s] // 512:ps[s + 1] // 512] == s)
-            assert np.all(rc[want_rows // 512:] == -1)
-
-
-def test_rows_collect_one_pass_keeps_the_same_pairs(ops):
-    """trec_topk_rows_collect: per superblock the same SET of users as the two-pass compaction (the order follows the
-    atomics), the counts, the overflow flag when a superblock keeps more than the capacity."""
-    from tensorrec_amd import _native as N
-    rng = np.random.default_rng(12)
-    for n_sb, n_u, stride, rcap in ((37, 5000, 5000, 2048), (130, 2050, 2051, 1024), (9, 3000, 3000, 512)):
-        table = rng.standard_normal((n_sb, stride)).astype(np.float32)
-        thr = rng.uniform(0.5, 2.5, n_u).astype(np.float32)
-        thr[5] = -np.inf
-        uerr = rng.uniform(0.0, 0.3, (n_u, 4)).astype(np.float32)
-        sbs = rng.uniform(0.0, 1.0, (n_sb, 4)).astype(np.float32)
-        with np.errstate(invalid="ignore", over="ignore"):
-            f32, f64 = np.float32, np.float64
-            infl, ck = f32(1.0029296875), f32(128 + 6) * f32(2.98023224e-07)
-            A = ((sbs[:, 2] + ck * sbs[:, 1]) * infl)[:, None]
-            B = (sbs[:, 1] * infl)[:, None]
-            C = (sbs[:, 3] * infl)[:, None]
-            cu = uerr[:, 2] * infl + f32(2e-30)
-
-            def pred(x):
-                y = np.nextafter(x, f32(-np.inf))
-                y[x == -np.inf] = -np.inf
-                return y
-            f = pred(pred(pred(thr.copy())) - cu)
-            fma = lambda a, b, c: (a.astype(f64) * b.astype(f64) + c.astype(f64)).astype(f32)
-            tv = table[:, :n_u]
-            lhs = fma(np.broadcast_to(uerr[:, 0][None, :], tv.shape), np.broadcast_to(A, tv.shape),
-                      fma(np.broadcast_to(uerr[:, 1][None, :], tv.shape), np.broadcast_to(B, tv.shape),
-                          fma(np.broadcast_to(uerr[:, 3][None, :], tv.shape), np.broadcast_to(C, tv.shape), tv)))
-            keep = ~(lhs < f[None, :])
+        assert keep[:, 5].all() and not keep[:, 6].any()
+        if rcap >= n_u:
+            assert keep[3].sum() == n_u - 1
         row_count = torch.zeros((n_sb,), dtype=torch.int32, device="cuda")
         row_user = torch.full((n_sb * rcap,), -7, dtype=torch.int32, device="cuda")
         status = torch.full((2,), -5, dtype=torch.int64, device="cuda")
@@ -618,12 +563,10 @@ def test_prerefined_threshold_keeps_fewer_pairs_and_the_same_lists(ops, d, n_u, 
 
 
 @pytest.mark.parametrize("d,biased,n_u,n_i", [(128, True, 5000, 300_000), (64, False, 3000, 280_000 + 77), (128, True, 700, 1_000_000)])
-def test_cascade_with_the_item_resident_refining_kernel(ops, d, biased, n_u, n_i):
-    """tuning refine_resident = 1: the refining launches keep a superblock's 512 items in registers and stream its user list in
-    segments (csrc/refine_resident.hip) -- same maxima, same candidate lists, so the same exact result as the oracle's
-    tf.matmul + tf.nn.top_k (prediction_graphs.py:49-50, recommendation_graphs.py:80); segments of 64 users make every superblock
-    span several workgroups, the last catalogue ends inside a superblock."""
-    from tensorrec_amd import _native as N
+def test_cascade_refining_launches_on_full_and_partial_superblocks(ops, d, biased, n_u, n_i):
+    """The default refining launches (the user-resident kernel: trec_score_gemm_refine_candidates and its marking form) list the
+    candidates and the finish gives the same exact result as the oracle's tf.matmul + tf.nn.top_k (prediction_graphs.py:49-50,
+    recommendation_graphs.py:80): biased and unbiased, a catalogue that ends inside a superblock, 1M items for few users."""
     rng = np.random.default_rng(d + n_u)
     k = 10
     u = rng.standard_normal((n_u, d)).astype(np.float32)
@@ -631,13 +574,6 @@ def test_cascade_with_the_item_resident_refining_kernel(ops, d, biased, n_u, n_i
     ub = (0.1 * rng.standard_normal(n_u)).astype(np.float32) if biased else None
     ib = (0.1 * rng.standard_normal(n_i)).astype(np.float32) if biased else None
     rv, ri = O.topk_rows(O.score_dense_exact(u, v, ub, ib), k)
-    try:
-        for seg in (2048, 64):
-            N.set_tuning("refine_resident", 1)
-            N.set_tuning("refine_resident_seg", seg)
-            vals, idx, stats, _, _ = run_cascade(ops, u, v, k, ub, ib)
-            assert np.array_equal(idx, ri) and np.array_equal(vals, rv), (seg, stats)
-            assert stats["prefilter"] == "int8" and stats["tail"] == "candidate lists" and stats["flagged_users"] <= n_u // 20, stats
-    finally:
-        N.set_tuning("refine_resident", 0)
-        N.set_tuning("refine_resident_seg", 2048)
+    vals, idx, stats, _, _ = run_cascade(ops, u, v, k, ub, ib)
+    assert np.array_equal(idx, ri) and np.array_equal(vals, rv), stats
+    assert stats["prefilter"] == "int8" and stats["tail"] == "candidate lists" and stats["flagged_users"] <= n_u // 20, stats
