@@ -11,7 +11,8 @@
 // prediction), the interactions enter as their sparse list -- "all minus the positives" gives the negatives' moments -- and the
 // backward pass is one streaming write of the dense gradient plus a scatter over the interactions.  Sums are accumulated in
 // double (per thread, per wave by shuffles, one atomicAdd per workgroup), so the result does not depend on the reduction order
-// beyond 1e-12; the tests hold it to 1e-5 of the reference's own arithmetic (fixtures made by running the reference's source).
+// beyond 1e-12; the model tests hold it to 1e-5 of the reference's own arithmetic (fixtures made by running the reference's source),
+// tests/test_gpu_dense_losses.py holds every entry point to 1e-11 of a float64 restatement (st, coef) and to float32 rounding (outputs).
 #include "common.hpp"
 #include <math.h>
 
@@ -189,13 +190,15 @@ __global__ __launch_bounds__(256) void rmse_dense_bwd_pairs_kernel(int64_t ld, c
 //     dX = A X (Y^T Y) + B 1 (sum y)^T,   dY = A Y (X^T X) + B 1 (sum x)^T,
 // plus the corrections at the interaction cells, which flow through the serial predictions.
 
-// G[D, D] += X^T X over a slice of rows (double accumulation; X float [n, ld]); one workgroup = one 32 x 32 tile of G x one slice
+// G[D, D] += X^T X over a slice of rows (double accumulation; X float [n, ld]); one workgroup = one 32 x 32 tile of G x one slice.
+// Only the entries on and above the diagonal are accumulated: the slices' sums arrive in any order, and two atomicAdd chains
+// over the same values do not round alike, so the lower triangle is copied afterwards (gram_mirror_kernel) -- G == G^T bit for bit.
 __global__ __launch_bounds__(256) void gram_f64_kernel(const float* __restrict__ X, int64_t n, int D, int64_t ld,
                                                       int64_t rows_per_slice, double* __restrict__ G)
 {
     __shared__ float As[32][33], Bs[32][33];
     const int ti = blockIdx.x, tj = blockIdx.y;
-    if (tj < ti) return;                                  // G is symmetric: the upper triangle of tiles is computed, mirrored below
+    if (tj < ti) return;                                  // G is symmetric: the upper triangle of tiles is computed
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int64_t r0 = (int64_t)blockIdx.z * rows_per_slice;
     const int64_t r1 = r0 + rows_per_slice < n ? r0 + rows_per_slice : n;
@@ -222,11 +225,17 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int gi = ti * 32 + 2 * ty + i, gj = tj * 32 + 2 * tx + j;
-            if (gi < D && gj < D) {
-                atomicAdd(G + (int64_t)gi * D + gj, acc[i][j]);
-                if (tj != ti) atomicAdd(G + (int64_t)gj * D + gi, acc[i][j]);
-            }
+            if (gi <= gj && gj < D) atomicAdd(G + (int64_t)gi * D + gj, acc[i][j]);
         }
+}
+
+// G[i][j] = G[j][i] below the diagonal
+__global__ __launch_bounds__(256) void gram_mirror_kernel(double* __restrict__ G, int D)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= D * D) return;
+    const int i = e / D, j = e % D;
+    if (j < i) G[e] = G[(int64_t)j * D + i];
 }
 
 // st[0] += sum p, st[1] += sum (p - mu)^2 over n predictions whose plain sums are m = {sum p, sum p^2}
@@ -361,6 +370,7 @@ extern "C" int trec_gram_f64(const float* X, int64_t n, int32_t D, int64_t ld, d
     slices = ceil_div64(n, per);
     TREC_REQUIRE(slices <= 65535, "trec_gram_f64: too many row slices");
     hipLaunchKernelGGL(gram_f64_kernel, dim3((unsigned)tiles, (unsigned)tiles, (unsigned)slices), dim3(256), 0, s, X, n, (int)D, ld, per, G);
+    if (D > 1) hipLaunchKernelGGL(gram_mirror_kernel, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, s, G, (int)D);
     return trec_check_launch("trec_gram_f64");
 }
 
