@@ -744,6 +744,13 @@ int trec_topk_rows_excluded(float* scores, int64_t ld, int64_t n_rows, int64_t n
 int trec_exclude_rank_adjust(const int64_t* pair_ptr, const int32_t* t_idx, const float* t_score, const int64_t* ex_ptr,
                              const int32_t* ex_idx, const float* ex_score, int64_t n_users, int32_t* counts, void* stream);
 
+/* ---- EXTENSION: item-item top-k without the query item (csrc/exclude.hip, docs/similar_items.md; no TF counterpart) ----
+ * trec_topk_drop_self: in_vals / in_idx [n_rows, kf] (2 <= kf <= 1025) = every row's exact top-kf (value desc, index asc, places
+ * beyond the catalogue -inf / -1) -> out [n_rows, kf - 1]: the row without its FIRST entry whose id is self_id[row], order and
+ * padding kept.  A row that does not hold self_id[row] (kf other items tie with or beat it) keeps its first kf - 1 entries.     */
+int trec_topk_drop_self(const float* in_vals, const int32_t* in_idx, int32_t kf, int64_t n_rows, const int32_t* self_id,
+                        float* out_vals, int32_t* out_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,7 @@ SIGNATURES = {
     "trec_exclude_filter_topk": [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "trec_topk_rows_excluded": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "trec_exclude_rank_adjust": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "trec_topk_drop_self": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -25,6 +25,10 @@
 // 3. trec_exclude_rank_adjust.  Pair ranks counted over every item (K2r, trec_rank_of_pairs_by_user) minus the excluded items
 //    ahead of the target, with K2r's rule: counts[t] -= #{x in E_u : s_x > s_t or (s_x == s_t and x < t)}.  One wave per user;
 //    the scores of both sides must come from the same chain as the count (trec_pair_score_exact, or the score slab itself).
+//
+// 4. trec_topk_drop_self (predict_similar_items_top_k(exclude_self=True), docs/similar_items.md).  The item-item lists are fetched
+//    with one place more than asked for; one wave per row copies the [n, k + 1] list to [n, k] without the first entry whose id is
+//    the row's query item.  A row that does not hold its query (k + 1 other items tie with or beat it) keeps its first k entries.
 #include "topk_common.hpp"
 
 namespace {
@@ -93,6 +97,42 @@ __global__ __launch_bounds__(256) void exclude_filter_kernel(const float* __rest
         const bool redo = kept < k && ii[kf - 1] >= 0;
         flag[u] = redo ? 1 : 0;
         if (redo) atomicAdd(n_flagged, 1);
+    }
+}
+
+// one wave per row: entry j of the [n_rows, kf] list goes to place j when it stands before the row's first entry holding
+// self_id[row], to place j - 1 when it stands behind it, and that entry itself nowhere; without such an entry the last one falls off
+__global__ __launch_bounds__(256) void drop_self_kernel(const float* __restrict__ in_vals, const int32_t* __restrict__ in_idx, int kf,
+                                                        int64_t n_rows, const int32_t* __restrict__ self_id,
+                                                        float* __restrict__ out_vals, int32_t* __restrict__ out_idx)
+{
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= n_rows) return;
+    const int lane = lane_id();
+    const int k = kf - 1;
+    const int32_t self = self_id[u];
+    const float* iv = in_vals + u * kf;
+    const int32_t* ii = in_idx + u * kf;
+    float* ov = out_vals + u * k;
+    int32_t* oi = out_idx + u * k;
+    int at = kf;                                                    // wave-uniform: place of the dropped entry (kf: none so far)
+    for (int j0 = 0; j0 < kf; j0 += TREC_WAVE) {
+        const int j = j0 + lane;
+        int32_t id = -1;
+        float v = -INFINITY;
+        if (j < kf) {
+            id = ii[j];
+            v = iv[j];
+        }
+        if (at == kf) {
+            const unsigned long long mask = __ballot(j < kf && id >= 0 && id == self);
+            if (mask != 0ull) at = j0 + (int)__builtin_ctzll(mask);
+        }
+        const int dst = j < at ? j : j - 1;
+        if (j < kf && j != at && dst < k) {
+            ov[dst] = v;
+            oi[dst] = id;
+        }
     }
 }
 
@@ -371,6 +411,18 @@ extern "C" int trec_exclude_filter_topk(const float* in_vals, const int32_t* in_
     hipLaunchKernelGGL(exclude_filter_kernel, dim3((unsigned)ceil_div64(n_users, 4)), dim3(256), 0, (hipStream_t)stream, in_vals, in_idx,
                        kf, n_users, k, ex_ptr, ex_idx, rows, out_vals, out_idx, flag, n_flagged);
     return trec_check_launch("trec_exclude_filter_topk");
+}
+
+extern "C" int trec_topk_drop_self(const float* in_vals, const int32_t* in_idx, int32_t kf, int64_t n_rows, const int32_t* self_id,
+                                   float* out_vals, int32_t* out_idx, void* stream)
+{
+    TREC_REQUIRE(in_vals && in_idx && self_id && out_vals && out_idx, "trec_topk_drop_self: null pointer");
+    TREC_REQUIRE(kf >= 2 && kf <= SEL_THREADS + 1, "trec_topk_drop_self: need 2 <= kf <= 1025");
+    TREC_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffLL, "trec_topk_drop_self: bad row count");
+    if (n_rows == 0) return TREC_OK;
+    hipLaunchKernelGGL(drop_self_kernel, dim3((unsigned)ceil_div64(n_rows, 4)), dim3(256), 0, (hipStream_t)stream, in_vals, in_idx, kf,
+                       n_rows, self_id, out_vals, out_idx);
+    return trec_check_launch("trec_topk_drop_self");
 }
 
 extern "C" int trec_topk_rows_excluded(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols, int32_t k, const int64_t* ex_ptr,

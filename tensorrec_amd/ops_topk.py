@@ -1400,6 +1400,23 @@ def exclude_filter_topk(vals, idx, k, ex_ptr, ex_idx, rows=None):
     return ov, oi, flag, n_flag
 
 
+def topk_drop_self(vals, idx, self_ids):
+    """predict_similar_items_top_k(exclude_self=True) (csrc/exclude.hip): exact top-(k + 1) lists [n, k + 1] -> [n, k] without each
+    row's first entry whose id is ``self_ids[row]`` (device int32 [n]); a row that does not hold it keeps its first k entries.
+    Order and -inf / -1 padding are kept; 2 <= k + 1 <= EXCLUDE_K_MAX + 1."""
+    vals, idx = vals.contiguous(), idx.contiguous()
+    n, kf = idx.shape
+    if not 2 <= int(kf) <= EXCLUDE_K_MAX + 1:
+        raise ValueError("topk_drop_self supports lists of 2 .. %d places (got %d)" % (EXCLUDE_K_MAX + 1, kf))
+    if self_ids.dtype != torch.int32 or self_ids.numel() != n:
+        raise ValueError("topk_drop_self needs one int32 id per row")
+    ov = torch.empty((n, int(kf) - 1), dtype=torch.float32, device=idx.device)
+    oi = torch.empty((n, int(kf) - 1), dtype=torch.int32, device=idx.device)
+    with _timed("topk_drop_self"):
+        N.call("trec_topk_drop_self", N.ptr(vals), N.ptr(idx), int(kf), n, N.ptr(self_ids.contiguous()), N.ptr(ov), N.ptr(oi))
+    return ov, oi
+
+
 def topk_rows_excluded(scores, k, ex_ptr=None, ex_idx=None, rows=None):
     """Exact top-k (k <= 1024) of every row of a score slab with the row's excluded columns skipped: (values [n, k], ids int32
     [n, k]) in rank_predictions' order, -inf / -1 beyond the row's non-excluded entries (csrc/exclude.hip).  The excluded cells

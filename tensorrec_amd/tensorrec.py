@@ -27,6 +27,7 @@ from scipy import sparse as sp
 
 from . import ops
 from . import exclusion as _excl
+from . import similar as _sim
 from . import _native as N
 from .errors import (
     ModelNotBiasedException, ModelNotFitException, ModelWithoutAttentionException, BatchNonSparseInputException
@@ -106,6 +107,7 @@ def _to_host(t):
     ``predict_rank``) are copied into page-locked memory, where the DMA engines run at PCIe rate instead of staging
     through the runtime's bounce buffer (~7 GB/s from pageable memory); the array keeps the pinned block alive and
     torch's host allocator recycles it when the caller drops the array."""
+    t = t.detach()            # (identity features alias the weight tables: a representation may BE a parameter)
     nbytes = t.numel() * t.element_size()
     if not t.is_cuda or nbytes < (16 << 20) or nbytes > (8 << 30):
         return t.cpu().numpy()
@@ -1222,13 +1224,11 @@ class TensorRec(object):
         "n_excluded", "n_fallback"}.  None, or a matrix without a non-zero entry: exactly the call without it.  Not with
         ``item_sharded`` / ``item_offset`` (a follow-up: filter after the replicated merge, tier 2 per shard) and not beyond
         k = 1,024 (ValueError)."""
-        from . import sharding
         self._check_fit('predict_top_k')
         if int(k) < 1:
             raise ValueError("predict_top_k needs k >= 1 (got %r)" % (k,))
         if not self._is_engine_graph():
             raise ValueError("predict_top_k needs a built-in prediction graph")
-        graph = self.prediction_graph_factory
         uf, itf = self._inference(user_features, item_features)
         ex = None
         if exclude is not None:
@@ -1240,19 +1240,44 @@ class TensorRec(object):
                     raise ValueError("predict_top_k(exclude=...) supports k <= %d (got %d)" % (ops.EXCLUDE_K_MAX, int(k)))
                 dev = self._store.device
                 ex = {"indptr": ex_indptr, "ptr": torch.from_numpy(ex_indptr).to(dev),
-                      "idx": torch.from_numpy(ex_indices).to(dev), "k_fetch": int(k), "n_fallback": 0}
+                      "idx": torch.from_numpy(ex_indices).to(dev), "k_fetch": int(k), "n_fallback": 0,
+                      "n_excluded": int(len(ex_indices))}
+        with torch.no_grad(), variable_scope(self._store):
+            user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
+            return self._topk_routed(user_reprs, attn_reprs, item_repr, user_bias if self.biased else None,
+                                     item_bias if self.biased else None, k, batch_size=user_batch_size, return_device=return_device,
+                                     item_sharded=item_sharded, item_offset=item_offset, return_route=return_route, ex=ex)
+
+    def _topk_routed(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias, k, batch_size=None, return_device=False,
+                     item_sharded=False, item_offset=0, return_route=False, ex=None, drop_self=None, similar=None):
+        """The one routing core of the exact top-k calls (predict_top_k, predict_similar_items_top_k), entered once the
+        representations exist: the route predicates, the item-side operands (prepared once, shared by every batch), the batch loop
+        with its out-of-memory halving, and ``last_route``.  ``query_reprs``: one [n_queries, d] representation per taste (the
+        users of predict_top_k; rows of the item representation for item-item lists); ``attn_reprs``: the attention representations
+        or None; ``query_bias`` / ``item_bias``: projected biases, None for none -- the core never reads ``self.biased``.  ``ex``:
+        predict_top_k's exclusions.  ``drop_self`` (device int32 [n_queries], not together with ``ex``): the id to leave out of
+        each row -- the route is chosen for, and run with, k + 1 places and trec_topk_drop_self reduces the lists to k; the slab
+        route masks its slabs instead.  Runs inside the caller's ``torch.no_grad()`` / variable scope."""
+        from . import sharding
+        graph = self.prediction_graph_factory
+        n_q, n_i = int(query_reprs[0].shape[0]), int(item_repr.shape[0])
+        multi = len(query_reprs) > 1 or attn_reprs is not None
+        # the places the routes are chosen for and asked for (exclusions over-fetch per batch, inside the chosen route: fetch_k below)
+        k_public, user_batch_size = int(k), batch_size
+        if drop_self is not None:
+            k = _sim.k_fetch(k_public, True)
         dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
         want_sq = graph.engine_mode == ops.MODE_EUCLIDEAN
         # attention models: the softmax-weighted sum over tastes (recommendation_graphs.py:98-107) does not decompose into
         # per-taste top-k lists, but it IS independent per (user, item): score slabs of a few thousand users through the
         # collapse kernel (K9), exact ranks pick the k best of every row -- and item shards merge like any other top-k
-        slab_route = self.attention_graph_factory is not None or self.n_components > ops.SCORE_KMAX
+        slab_route = attn_reprs is not None or self.n_components > ops.SCORE_KMAX
         import torch.distributed as dist
         sharded = bool(item_sharded) and sharding.active(self.process_group)
         method, floor_exchange = "auto", None
         if sharded:
             # every rank must take the same code path (the floor exchange is a collective): decide on the smallest shard
-            smallest = torch.tensor([itf.shape[0]], dtype=torch.int64, device=self._store.device)
+            smallest = torch.tensor([n_i], dtype=torch.int64, device=self._store.device)
             dist.all_reduce(smallest, op=dist.ReduceOp.MIN, group=self.process_group)
             if int(smallest.item()) >= ops.TWO_STAGE_MIN_ITEMS:
                 method = "two_stage"
@@ -1264,7 +1289,7 @@ class TensorRec(object):
                 method = "direct"
         # precision='fp32' on a large catalogue: the same exact fp32 result, with the contraction done once on bf16 MFMA
         # as an error-bounded filter and only the survivors re-scored in fp32 (ops.score_topk_filtered)
-        n_items_min = int(smallest.item()) if sharded else itf.shape[0]
+        n_items_min = int(smallest.item()) if sharded else n_i
         filtered = (dtype == ops.DTYPE_F32 and graph.engine_mode == ops.MODE_DOT and 1 <= k <= 16 and
                     n_items_min >= ops.TWO_STAGE_MIN_ITEMS and self.n_components <= 256 and
                     ops.N.load().trec_get_tuning(b"topk_bf16_filter", 1) != 0)
@@ -1306,22 +1331,26 @@ class TensorRec(object):
         elif wide:
             route_name = "wide_cascade"
         else:
-            route_name = method if method != "auto" else ("two_stage" if itf.shape[0] >= ops.TWO_STAGE_MIN_ITEMS else "direct")
+            route_name = method if method != "auto" else ("two_stage" if n_i >= ops.TWO_STAGE_MIN_ITEMS else "direct")
         # exclusions: the lists are asked for k' places (the same route's largest k at most)
-        k_all = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], 0, uf.shape[0]))
+        k_all = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], 0, n_q))
         if user_batch_size is None:
             route = "wide" if (wide or (euclid_filtered and k > ops.EUCLID_CANDIDATES - 4)) else \
                 ("cascade" if (filtered or euclid_filtered) else "two_stage")
-            user_batch_size = ops.topk_user_batch(uf.shape[0], itf.shape[0], self.n_components, self._store.device,
+            user_batch_size = ops.topk_user_batch(n_q, n_i, self.n_components, self._store.device,
                                                   route=route, k=k_all)
             if sharded:                  # every rank walks the SAME user batches (each batch holds collectives): the smallest wins
                 ubs = torch.tensor([user_batch_size], dtype=torch.int64, device=self._store.device)
                 dist.all_reduce(ubs, op=dist.ReduceOp.MIN, group=self.process_group)
                 user_batch_size = int(ubs.item())
-        self.last_route = {"route": route_name, "k": int(k), "sharded": bool(sharded), "n_items": int(itf.shape[0]),
+        self.last_route = {"route": route_name, "k": k_public, "sharded": bool(sharded), "n_items": n_i,
                            "user_batch_size": int(user_batch_size), "precision": self.precision}
         if ex is not None:
-            self.last_route["exclude"] = {"k_fetch": int(k), "n_excluded": int(len(ex_indices)), "n_fallback": 0}
+            self.last_route["exclude"] = {"k_fetch": int(k), "n_excluded": ex["n_excluded"], "n_fallback": 0}
+        if similar is not None:
+            # (the slab route masks the query's own column in its slabs: k places, nothing fetched on top)
+            k = _sim.k_fetch(k_public, drop_self is not None, slab_route)
+            self.last_route["similar"] = dict(similar, k_fetch=int(k))
 
         def _ret(v_, i_):
             if ex is not None:
@@ -1330,77 +1359,85 @@ class TensorRec(object):
         vals, idx = [], []
         if slab_route:
             # (also: representations wider than the fused kernels' resident operand -- K-looped fp32 GEMM slabs)
-            planes = 1 + (2 * self.n_tastes if self.attention_graph_factory is not None else
-                          (self.n_tastes if self._multi() else 0))
-            step = max(1, min(int(user_batch_size), (1 << 28) // max(1, itf.shape[0] * planes)))
+            planes = 1 + (2 * len(query_reprs) if attn_reprs is not None else (len(query_reprs) if multi else 0))
+            step = max(1, min(int(user_batch_size), (1 << 28) // max(1, n_i * planes)))
             if sharded:                  # (each batch ends in a collective: every rank takes the same steps)
                 st = torch.tensor([step], dtype=torch.int64, device=self._store.device)
                 dist.all_reduce(st, op=dist.ReduceOp.MIN, group=self.process_group)
                 step = int(st.item())
-            with torch.no_grad(), variable_scope(self._store):
-                user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
-                for s in range(0, uf.shape[0], step):
-                    e = min(s + step, uf.shape[0])
-                    ub = user_bias[s:e] if user_bias is not None else None
-                    if self._multi():
-                        attn = [a[s:e] for a in attn_reprs] if attn_reprs is not None else None
-                        slab = self._dense_multi([u[s:e] for u in user_reprs], attn, item_repr, ub, item_bias)
+            for s in range(0, n_q, step):
+                e = min(s + step, n_q)
+                qb = query_bias[s:e] if query_bias is not None else None
+                attn = [a[s:e] for a in attn_reprs] if attn_reprs is not None else None
+                slab = self._score_slab([q[s:e] for q in query_reprs], attn, item_repr, qb, item_bias)
+                if ex is not None:       # (the slab route needs no over-fetch: its slabs are masked directly)
+                    v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"][s:], ex["idx"])
+                elif drop_self is not None:      # (one excluded column per row: the query's own)
+                    own_ptr = torch.arange(e - s + 1, dtype=torch.int64, device=slab.device)
+                    v, i = ops.topk_rows_excluded(slab.contiguous(), k, own_ptr, drop_self[s:e].contiguous())
+                else:
+                    v, i = ops.topk_from_scores(slab.contiguous(), k)
+                i = torch.where(i >= 0, i + int(item_offset), i)
+                if sharded:
+                    if sharding.a2a_available(v, self.process_group):
+                        v, i = sharding.sharded_top_k_a2a(v, i, k, self.process_group, replicate=True)
                     else:
-                        slab = self._dense_prediction(user_reprs[0][s:e], item_repr, ub, item_bias)
-                    if ex is not None:       # (the slab route needs no over-fetch: its slabs are masked directly)
-                        v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"][s:], ex["idx"])
-                    else:
-                        v, i = ops.topk_from_scores(slab.contiguous(), k)
-                    i = torch.where(i >= 0, i + int(item_offset), i)
-                    if sharded:
-                        if sharding.a2a_available(v, self.process_group):
-                            v, i = sharding.sharded_top_k_a2a(v, i, k, self.process_group, replicate=True)
-                        else:
-                            v, i = sharding.sharded_top_k(v, i, k, self.process_group)
-                    vals.append(v)
-                    idx.append(i)
-            vals, idx = torch.cat(vals), torch.cat(idx)
-            return _ret(vals, idx) if return_device else _ret(_to_host(vals), _to_host(idx))
-        with torch.no_grad(), variable_scope(self._store):
-            user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
-            ib = item_bias.contiguous() if self.biased else None
-            if filtered or wide:
-                i_f = ops.score_prep_filter(item_repr, normalize=graph.engine_normalize, bias=ib, want_gstats=True)
-            if not filtered and not wide:         # (the wide route works on the filter operand alone)
-                i_op, i_sq, kpad = ops.score_prep(item_repr, dtype, normalize=graph.engine_normalize, want_sqnorm=want_sq)
-            s = 0
-            while s < uf.shape[0]:
-                e = min(s + user_batch_size, uf.shape[0])
-                retry = False
-                k_b = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], s, e))
-                try:
-                    v, i = self._topk_user_batch(s, e, user_reprs, item_repr, user_bias, ib, k_b, graph, dtype, want_sq, filtered,
-                                                 euclid_filtered, prefilter, sharded, method, floor_exchange, stats_exchange,
-                                                 item_offset, i_f if (filtered or wide) else None,
-                                                 None if (filtered or wide) else (i_op, i_sq, kpad), wide=wide)
-                except torch.cuda.OutOfMemoryError:
-                    # the workspace model of ops.topk_user_batch was too optimistic for this device's state: half the users per
-                    # pass (item shards: the ranks walk the same batches and a rank cannot shrink alone -- the error stands)
-                    if sharded or e - s <= 4096:
-                        raise
-                    retry = True
-                if retry:
-                    # (outside the except block: the traceback no longer pins the failed call's tensors, so the cache really is
-                    # returned; halved from the size that RAN -- the nominal one may exceed the users that were left)
-                    torch.cuda.empty_cache()
-                    user_batch_size = max(4096, min(user_batch_size, e - s) // 2)
-                    continue
-                if ex is not None:
-                    v, i = self._exclude_batch(s, e, v, i, k, ex, user_reprs, attn_reprs, item_repr, user_bias, item_bias)
-                    ex["k_fetch"] = max(ex["k_fetch"], k_b)
+                        v, i = sharding.sharded_top_k(v, i, k, self.process_group)
                 vals.append(v)
                 idx.append(i)
-                s = e
+            vals, idx = torch.cat(vals), torch.cat(idx)
+            return _ret(vals, idx) if return_device else _ret(_to_host(vals), _to_host(idx))
+        ib = item_bias.contiguous() if item_bias is not None else None
+        if filtered or wide:
+            i_f = ops.score_prep_filter(item_repr, normalize=graph.engine_normalize, bias=ib, want_gstats=True)
+        if not filtered and not wide:         # (the wide route works on the filter operand alone)
+            i_op, i_sq, kpad = ops.score_prep(item_repr, dtype, normalize=graph.engine_normalize, want_sqnorm=want_sq)
+        s = 0
+        while s < n_q:
+            e = min(s + user_batch_size, n_q)
+            retry = False
+            k_b = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], s, e))
+            try:
+                v, i = self._topk_user_batch(s, e, query_reprs, item_repr, query_bias, ib, k_b, graph, dtype, want_sq, filtered,
+                                             euclid_filtered, prefilter, sharded, method, floor_exchange, stats_exchange,
+                                             item_offset, i_f if (filtered or wide) else None,
+                                             None if (filtered or wide) else (i_op, i_sq, kpad), wide=wide)
+            except torch.cuda.OutOfMemoryError:
+                # the workspace model of ops.topk_user_batch was too optimistic for this device's state: half the users per
+                # pass (item shards: the ranks walk the same batches and a rank cannot shrink alone -- the error stands)
+                if sharded or e - s <= 4096:
+                    raise
+                retry = True
+            if retry:
+                # (outside the except block: the traceback no longer pins the failed call's tensors, so the cache really is
+                # returned; halved from the size that RAN -- the nominal one may exceed the users that were left)
+                torch.cuda.empty_cache()
+                user_batch_size = max(4096, min(user_batch_size, e - s) // 2)
+                continue
+            if ex is not None:
+                v, i = self._exclude_batch(s, e, v, i, k, ex, query_reprs, attn_reprs, item_repr, query_bias, item_bias)
+                ex["k_fetch"] = max(ex["k_fetch"], k_b)
+            if drop_self is not None:            # [n, k + 1] -> [n, k] without the query's own entry (csrc/exclude.hip)
+                v, i = ops.topk_drop_self(v, i, drop_self[s:e])
+            vals.append(v)
+            idx.append(i)
+            s = e
         vals, idx = torch.cat(vals), torch.cat(idx)
         self.last_route["user_batch_size"] = int(user_batch_size)          # (after any out-of-memory halving)
         if return_device:
             return _ret(vals, idx)
         return _ret(_to_host(vals), _to_host(idx))
+
+    def _score_slab(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias):
+        """[n_queries, n_items] scores of the slab passes of the top-k core, with the biases it is GIVEN (None: none): one taste is
+        _dense_prediction's engine call; tastes / attention go through _dense_multi, which only predict_top_k reaches."""
+        if len(query_reprs) > 1 or attn_reprs is not None:
+            return self._dense_multi(query_reprs, attn_reprs, item_repr, query_bias, item_bias)
+        graph = self.prediction_graph_factory
+        dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
+        qb = query_bias.detach().contiguous() if query_bias is not None else None
+        ib = item_bias.detach().contiguous() if item_bias is not None else None
+        return ops.dense_scores(query_reprs[0], item_repr, dtype, graph.engine_normalize, graph.engine_mode, qb, ib)
 
     def _exclude_batch(self, s, e, v, i, k, ex, user_reprs, attn_reprs, item_repr, user_bias, item_bias):
         """Users [s, e) of predict_top_k(exclude=...): their exact top-k' lists -> the first k non-excluded entries (tier 1), and
@@ -1418,20 +1455,18 @@ class TensorRec(object):
 
     def _topk_excluded_slabs(self, users, user_reprs, attn_reprs, item_repr, user_bias, item_bias, k, ex):
         """Exact top-k of the given users (device int64 ids) with their excluded items skipped: score slabs of the slab route's
-        code (_dense_prediction / _dense_multi, same dtype) and the masked selection of csrc/exclude.hip."""
+        code (_score_slab, same dtype) and the masked selection of csrc/exclude.hip."""
         n_i = item_repr.shape[0]
-        planes = 1 + (2 * self.n_tastes if attn_reprs is not None else (self.n_tastes if self._multi() else 0))
+        n_t = len(user_reprs)
+        planes = 1 + (2 * n_t if attn_reprs is not None else (n_t if n_t > 1 else 0))
         step = max(1, (1 << 28) // max(1, n_i * planes))
         rows32 = users.to(torch.int32)
         vals, idx = [], []
         for s in range(0, users.numel(), step):
             sel = users[s:s + step]
             ub = user_bias[sel] if user_bias is not None else None
-            if self._multi():
-                attn = [a[sel] for a in attn_reprs] if attn_reprs is not None else None
-                slab = self._dense_multi([u[sel] for u in user_reprs], attn, item_repr, ub, item_bias)
-            else:
-                slab = self._dense_prediction(user_reprs[0][sel], item_repr, ub, item_bias)
+            attn = [a[sel] for a in attn_reprs] if attn_reprs is not None else None
+            slab = self._score_slab([u[sel] for u in user_reprs], attn, item_repr, ub, item_bias)
             v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"], ex["idx"], rows=rows32[s:s + step].contiguous())
             vals.append(v)
             idx.append(i)
@@ -1442,7 +1477,7 @@ class TensorRec(object):
         """Users [s, e) of predict_top_k: every taste's exact top-k, merged, and (item shards) exchanged."""
         from . import sharding
         import torch.distributed as dist
-        ub = user_bias[s:e].contiguous() if self.biased else None
+        ub = user_bias[s:e].contiguous() if user_bias is not None else None
         if i_ops is not None:
             i_op, i_sq, kpad = i_ops
         per_taste = []
@@ -1481,7 +1516,7 @@ class TensorRec(object):
     @_on_model_device
     def predict_similar_items(self, item_features, item_ids, n_similar):
         """Most similar items, list of lists of (item_id, score) (tensorrec.py:666-703); the query item itself is
-        included, as in the reference."""
+        included, as in the reference.  predict_similar_items_top_k ranks on the device, for any number of query items."""
         self._check_fit('predict_similar_items')
         _, itf = self._inference(None, item_features)
         with torch.no_grad(), variable_scope(self._store):
@@ -1496,6 +1531,56 @@ class TensorRec(object):
             item_results = sorted(zip(best, item_sims[best]), key=lambda x: -x[1])
             results.append(item_results)
         return results
+
+    @_on_model_device
+    def predict_similar_items_top_k(self, item_features, item_ids=None, k=10, exclude_self=False, item_batch_size=None,
+                                    return_device=False, return_route=False):
+        """EXTENSION: the k most similar items of every query item -- (scores [Q, k] float32, item ids [Q, k] int32) -- ranked on
+        the device by the exact top-k routes of predict_top_k, without the [Q, n_items] matrix predict_similar_items brings to the
+        host (docs/similar_items.md).  Row q holds the first k places of row q of
+        ``recommendation_graphs.predict_similar_items(prediction_graph, item_repr, item_ids)`` -- the model's prediction graph
+        between the gathered rows and all rows, no biases, as in the reference -- in predict_top_k's order (score descending, ties
+        by ascending item id); places beyond the catalogue hold (-inf, -1).  fp32 models: values and ids bit-identical to that
+        definition; ``precision='bf16'``: the scores of the bf16 route, as in predict_top_k.
+
+        ``item_ids`` None: every item in order (Q = n_items; the item representation is sliced, not gathered).  Otherwise any
+        integer sequence or array -- repeats allowed, order kept; an id outside [0, n_items) raises ValueError before anything is
+        launched, an empty list returns (0, k) arrays.  ``exclude_self=True`` removes column ``item_ids[q]`` from row q before the
+        selection -- only that column: other items with an identical representation stay.  The route is then chosen for, and run
+        with, k + 1 places and one kernel drops the query's own entry from the lists (k <= 1,024); the slab route masks the column
+        in its score slabs instead.  ``item_batch_size``: queries per pass (None: ops.topk_user_batch decides).  Tastes and
+        attention belong to the user tower and do not enter.
+
+        ``last_route`` holds predict_top_k's keys and "similar": {"n_queries", "exclude_self", "k_fetch"}; ``return_route=True``
+        returns it as a third value."""
+        self._check_fit('predict_similar_items_top_k')
+        k = _sim.check_k(k)
+        if not self._is_engine_graph():
+            raise ValueError("predict_similar_items_top_k needs a built-in prediction graph")
+        exclude_self = bool(exclude_self)
+        if exclude_self and k > ops.EXCLUDE_K_MAX:
+            raise ValueError("predict_similar_items_top_k(exclude_self=True) supports k <= %d (got %d)" % (ops.EXCLUDE_K_MAX, k))
+        _, itf = self._inference(None, item_features)
+        ids64, ids32, all_items = _sim.query_ids(item_ids, itf.shape[0])
+        _sim.batch_plan(len(ids64), item_batch_size)                    # (validates item_batch_size)
+        similar = {"n_queries": int(len(ids64)), "exclude_self": exclude_self}
+        device = self._store.device
+        if len(ids64) == 0:
+            self.last_route = {"route": "none", "k": k, "sharded": False, "n_items": int(itf.shape[0]), "user_batch_size": 0,
+                               "precision": self.precision, "similar": dict(similar, k_fetch=k)}
+            vals = torch.empty((0, k), dtype=torch.float32, device=device)
+            idx = torch.empty((0, k), dtype=torch.int32, device=device)
+            out = (vals, idx) if return_device else (_to_host(vals), _to_host(idx))
+            return out + (dict(self.last_route),) if return_route else out
+        with torch.no_grad(), variable_scope(self._store):
+            item_repr, _ = self.item_repr_graph_factory.connect_representation_graph(
+                tf_features=itf, n_components=self.n_components, n_features=self.n_item_features,
+                node_name_ending='item')
+            query = item_repr if all_items else item_repr[torch.from_numpy(ids64).to(device)].contiguous()
+            own = torch.from_numpy(ids32).to(device) if exclude_self else None
+            return self._topk_routed([query], None, item_repr, None, None, k,
+                                     batch_size=None if item_batch_size is None else int(item_batch_size),
+                                     return_device=return_device, return_route=return_route, drop_self=own, similar=similar)
 
     @_on_model_device
     def predict_user_representation(self, user_features):
