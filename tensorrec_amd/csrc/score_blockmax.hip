@@ -10,10 +10,10 @@
 // runs the max-chain epilogue of a 32-item block between that block's last MFMA and the next block's first one: a
 // single wave keeps the matrix pipe ~50% busy and relies on its two SIMD neighbours for the rest (measured: 63%).
 // Here one 64-item tile is ONE straight-line pipeline of 2*KS steps, pinned with sched_barrier:
-//     step s:  ds_read for step s+2   |   2 MFMAs of step s   |   a slice of the max chain of the PREVIOUS 32-item block
-// so LDS latency hides behind two steps (128 MFMA cycles) and the epilogue of block b runs under the MFMAs of block
-// b+1 (two accumulator sets).  The epilogue of a tile's second block runs under the next tile's first block, across
-// the barrier; it is flushed early only at superblock ends (every 8th tile).
+//     step s:  ds_read for step s+2   |   4 MFMAs of step s   |   after a block's last step: its max chain
+// so LDS latency hides behind two steps (256 MFMA cycles); a wave owns 128 users, which leaves registers for ONE
+// accumulator set, and the max chain of a 32-item block runs right behind that block's last MFMAs, covered by the other
+// wave of the SIMD.
 //
 // Partial tiles need no masking: staging re-reads the last valid item row (and its bias) for rows past the end, and a
 // maximum is unchanged by duplicates.
@@ -30,28 +30,28 @@ __device__ __forceinline__ int swz16(int row, int ch) {
     return ch >= 16 ? (row & 15) : ((row >> 1) & 7);
 }
 
-// NCB: 32-user column blocks per wave (2: 256 users per workgroup, 2-3 workgroups per CU; 4: 512 users per workgroup,
-// one workgroup per CU -- half the LDS reads, tile loads and barriers per flop, the wave hides its own latencies)
-// OVL: two accumulator sets, the epilogue of a block under the next block's MFMAs (false: one set, the epilogue right
-// after the block -- the register plan that lets a wave own 96 users)
-// GRP (grouped form, stage 2 of the int8 cascade): workgroup w owns superblock rblock_chunk[w] only; its resident rows are
-// users row_index[w * rows + r] (-1 = padding row) and each maximum goes to blockmax[superblock][that user] -- the refined
-// entries of the table the int8 stage wrote.
-template <int KT, bool BIAS, int NCB, int WPS, bool OVL = true, int NBUF = 2, bool GRP = false>
-__global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
+// A wave owns four column blocks of 32 users (512 users per workgroup, two workgroups per CU: half the LDS reads, tile loads
+// and barriers per flop of a 64-user wave) and one accumulator set.  Item tiles are double-buffered in LDS.
+// Tried and measured slower at 1M x 1M x 128, biased, and deleted (profiles/r01_k2_ablation.txt, profiles/r02_stage1_ab.txt):
+//   two accumulator sets, the max chain of a block sliced under the next block's MFMAs: with 64 users per wave
+//   1290-1340 TF, with 128 users per wave and one workgroup per CU 1257 TF; 96 users per wave, one set: 1468 TF -- against
+//   1528 TF as shipped;
+//   a third LDS buffer (two tiles of MFMAs for a tile's loads to land): 166.7 ms against 164.6 ms -- a tile's loads already
+//   land within one tile of MFMAs, the third buffer only costs LDS.
+template <int KT, bool BIAS>
+__global__ __launch_bounds__(256, 2) void blockmax_pipe_kernel(ScoreParams p)
 {
+    constexpr int NCB = 4;                   // 32-user column blocks per wave
+    constexpr int NBUF = 2;                  // LDS buffers (the ring below is written for any count: see stage_wait)
     constexpr int RB = KT * 2;               // bytes per operand row
     constexpr int CH = RB / 16;              // 16-byte chunks per row
     constexpr int KS = KT / 16;              // MFMA k-steps per block
     constexpr int TILE_BYTES = BN * RB;
     constexpr int NSLOT = BN * CH / 256;     // 16-byte staging slots per thread per tile
     constexpr int NSTEP = 2 * KS;            // pipeline steps per tile
-    constexpr int NOPS = NCB * 8;            // epilogue ops of one block: 8 v_max3 per accumulator, folded into bm directly
-    constexpr int OPS = (NOPS + KS - 4) / (KS - 3);     // ops per step: the epilogue runs in local steps 1 .. KS-3
     static_assert(KT == 64 || KT == 128, "pipelined BLOCKMAX covers K = 64 / 128");
 
-    // NBUF LDS buffers: tile t is computed while tiles t+1 .. t+NBUF-1 are in flight (global_load_lds).  Two is the
-    // shipped form: a third buffer (two tiles of MFMAs for a tile's loads to land) measured 1.2% SLOWER.
+    // NBUF LDS buffers: tile t is computed while tiles t+1 .. t+NBUF-1 are in flight (global_load_lds)
     extern __shared__ __attribute__((aligned(16))) char smem[];    // [NBUF][TILE_BYTES] item tiles | [NBUF][BN] item biases
     float* side = (float*)(smem + NBUF * TILE_BYTES);
 
@@ -59,9 +59,8 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
-    const int rblock = GRP ? (int)blockIdx.x : (int)(blockIdx.x % p.n_rblocks);
-    const int chunk = GRP ? p.rblock_chunk[rblock] : (int)(blockIdx.x / p.n_rblocks);
-    if (GRP && chunk < 0) return;                                // idle workgroup of the grouped launch
+    const int rblock = blockIdx.x % p.n_rblocks;
+    const int chunk = blockIdx.x / p.n_rblocks;
     const int64_t r_base = ((int64_t)rblock * 4 + wave) * (NCB * 32);
     const int64_t t_begin = (int64_t)chunk * p.chunk_len;
     const int64_t t_end = (t_begin + p.chunk_len < p.n_t) ? t_begin + p.chunk_len : p.n_t;
@@ -70,15 +69,10 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
     // ---- resident user fragments, straight from global, once ----
     bf16x8 rfb[NCB][KS];
     float r_bias[NCB];
-    int32_t dst_user[GRP ? NCB : 1];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
         int64_t row = r_base + cb * 32 + l31;
         if (row >= p.n_r) row = p.n_r - 1;                       // clamped rows are never written
-        if (GRP) {
-            dst_user[cb] = p.row_index[row];
-            row = dst_user[cb] < 0 ? 0 : dst_user[cb];           // padding rows compute on user 0, never written
-        }
         const char* src = (const char*)p.R + row * (int64_t)RB;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) rfb[cb][ks] = *(const bf16x8*)(src + (ks * 2 + half) * 16);
@@ -143,20 +137,16 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
     // rows 32..63 of a tile: (l31 + 32) has the same swizzle for CH = 16 (row & 15); for CH = 8 the swizzle is
     // ((row >> 1) & 7) and 32 >> 1 = 16 leaves the low three bits alone as well -> one offset table serves both blocks.
 
-    f32x16 accA[NCB], accB[NCB];
+    f32x16 acc[NCB];
     float bm[NCB];
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-        bm[cb] = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { accA[cb][r] = -INFINITY; accB[cb][r] = -INFINITY; }
-    }
+    for (int cb = 0; cb < NCB; ++cb) bm[cb] = -INFINITY;
 
-    // one op of a block's epilogue: I = NCB*j + cb, j = 0..7:  bm = max3(bm, x[2j], x[2j+1]).  The user bias is added once
+    // one op of a block's epilogue: I = NCB*j + cb, j = 0..7:  bm = max3(bm, acc[2j], acc[2j+1]).  The user bias is added once
     // per superblock, after the maximum (fp32 addition is monotone: max_r fl(x_r + b) == fl(max_r x_r + b)).
-    auto epi_op = [&](int I, f32x16 (&x)[NCB]) {
+    auto epi_op = [&](int I) {
         const int cb = I % NCB, j = I / NCB;
-        bm[cb] = fmaxf(fmaxf(bm[cb], x[cb][2 * j]), x[cb][2 * j + 1]);
+        bm[cb] = fmaxf(fmaxf(bm[cb], acc[cb][2 * j]), acc[cb][2 * j + 1]);
     };
     auto read_c0 = [&](f32x16& c, const float* sdi) {      // item biases of the block's 16 rows of this half-wave
 #pragma unroll
@@ -165,70 +155,17 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
             c[4 * q] = tb4[0]; c[4 * q + 1] = tb4[1]; c[4 * q + 2] = tb4[2]; c[4 * q + 3] = tb4[3];
         }
     };
-    // the NCB MFMAs of one step (acc = mfma(items, users): lane & 31 is the user).  With biases the item bias row, read
-    // into the LAST accumulator, is the C operand of every first MFMA (the last one accumulates in place).
-    auto mfma_step = [&](f32x16 (&acc)[NCB], const bf16x8& tfv, int ks) __attribute__((always_inline)) {
-        if (ks == 0) {
-            if (BIAS) {
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
-                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfv, rfb[cb][0], acc[NCB - 1], 0, 0, 0);
-            } else {
-                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfv, rfb[cb][0], z, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-                acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfv, rfb[cb][ks], acc[cb], 0, 0, 0);
-        }
-    };
-
-    // one tile: 2*KS pipeline steps.  `buf` is a compile-time constant at the call site (LDS immediates).
+    // one tile: 2*KS pipeline steps (acc = mfma(items, users): lane & 31 is the user), every block's epilogue right after its
+    // last MFMA step.  `buf` is a compile-time constant at the call site (LDS immediates).  The item-bias row of a block is
+    // read straight into accumulator 0 (no staging registers): for block A at tile start, for block B as soon as block A's
+    // epilogue is done with accumulator 0 -- the other accumulators' max chains hide the LDS latency.  The first MFMA step
+    // then feeds every accumulator from it, accumulator 0 itself last (in place).
     auto tile_body = [&](auto bufc) __attribute__((always_inline)) {
         constexpr int buf = decltype(bufc)::value;
         const char* tb = smem + buf * TILE_BYTES;
         const float* sd = side + buf * BN + 4 * half;
         bf16x8 tf[3];
-        if (BIAS) read_c0(accA[NCB - 1], sd);
-        tf[0] = *(const bf16x8*)(tb + koff[0]);
-        tf[1] = *(const bf16x8*)(tb + koff[1]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < NSTEP; ++s) {
-            const int blk = s / KS, ks = s % KS;
-            // (1) LDS reads two steps ahead; block B's bias row once block B's accumulators are free
-            if (s + 2 < NSTEP)
-                tf[(s + 2) % 3] = *(const bf16x8*)(tb + ((s + 2) / KS) * 32 * RB + koff[(s + 2) % KS]);
-            if (BIAS && s == KS - 2) read_c0(accB[NCB - 1], sd + 32);
-            // (2) the MFMAs of this step
-            if (blk == 0) mfma_step(accA, tf[s % 3], ks);
-            else mfma_step(accB, tf[s % 3], ks);
-            // (3) a slice of the epilogue of the block BEFORE this one (B of the previous tile under A, A under B);
-            //     it starts one step late so that the block's last MFMA has landed
-#pragma unroll
-            for (int i = 0; i < OPS; ++i) {
-                const int I = (ks - 1) * OPS + i;
-                if (ks >= 1 && I < NOPS) {
-                    if (blk == 0) epi_op(I, accB);
-                    else epi_op(I, accA);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    // single accumulator set: same LDS pipeline, every block's epilogue right after its last MFMA step.  The item-bias
-    // row of a block is read straight into accumulator 0 (no staging registers): for block A at tile start, for block B
-    // as soon as block A's epilogue is done with accumulator 0 -- the other accumulators' max chains hide the LDS
-    // latency.  The first MFMA step then feeds every accumulator from it, accumulator 0 itself last (in place).
-    auto tile_body_single = [&](auto bufc) __attribute__((always_inline)) {
-        constexpr int buf = decltype(bufc)::value;
-        const char* tb = smem + buf * TILE_BYTES;
-        const float* sd = side + buf * BN + 4 * half;
-        bf16x8 tf[3];
-        if (BIAS) read_c0(accA[0], sd);
+        if (BIAS) read_c0(acc[0], sd);
         tf[0] = *(const bf16x8*)(tb + koff[0]);
         tf[1] = *(const bf16x8*)(tb + koff[1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -241,26 +178,26 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
                 if (BIAS) {
 #pragma unroll
                     for (int cb = NCB - 1; cb >= 0; --cb)
-                        accA[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][0], accA[0], 0, 0, 0);
+                        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][0], acc[0], 0, 0, 0);
                 } else {
                     const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb)
-                        accA[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][0], z, 0, 0, 0);
+                        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][0], z, 0, 0, 0);
                 }
             } else {
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
-                    accA[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][ks], accA[cb], 0, 0, 0);
+                    acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[s % 3], rfb[cb][ks], acc[cb], 0, 0, 0);
             }
             if (ks == KS - 1) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) epi_op(j * NCB, accA);                     // accumulator 0 first ...
-                if (BIAS && blk == 0) read_c0(accA[0], sd + 32);                       // ... then it takes block B's biases
+                for (int j = 0; j < 8; ++j) epi_op(j * NCB);                           // accumulator 0 first ...
+                if (BIAS && blk == 0) read_c0(acc[0], sd + 32);                        // ... then it takes block B's biases
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
 #pragma unroll
-                    for (int cb = 1; cb < NCB; ++cb) epi_op(j * NCB + cb, accA);
+                    for (int cb = 1; cb < NCB; ++cb) epi_op(j * NCB + cb);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -279,32 +216,19 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
     int buf = 0;
     for (int t = 0; t < n_tiles; ++t) {
         if (t + NBUF - 1 < n_tiles) stage_issue(t + NBUF - 1, (buf + NBUF - 1) % NBUF);
-        if (OVL) {
-            if (buf == 0) tile_body(std::integral_constant<int, 0>{});
-            else if (buf == 1 || NBUF == 2) tile_body(std::integral_constant<int, 1>{});
-            else tile_body(std::integral_constant<int, NBUF - 1>{});
-        } else {
-            if (buf == 0) tile_body_single(std::integral_constant<int, 0>{});
-            else if (buf == 1 || NBUF == 2) tile_body_single(std::integral_constant<int, 1>{});
-            else tile_body_single(std::integral_constant<int, NBUF - 1>{});
-        }
+        if (buf == 0) tile_body(std::integral_constant<int, 0>{});
+        else tile_body(std::integral_constant<int, 1>{});
 
         if (((t + 1) % p.sb_tiles) == 0 || t + 1 == n_tiles) {
-            // end of a superblock: finish block B now, combine the two half-wave maxima of each user, store, reset
-#pragma unroll
-            for (int I = 0; I < NOPS; ++I) if (OVL) epi_op(I, accB);
+            // end of a superblock: combine the two half-wave maxima of each user, store, reset
             const int64_t sb = t_begin / ((int64_t)p.sb_tiles * BN) + t / p.sb_tiles;
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
                 float v = fmaxf(bm[cb], __shfl_xor(bm[cb], 32, 64));
                 if (BIAS) v = v + r_bias[cb];
                 const int64_t u = r_base + cb * 32 + l31;
-                if (GRP) {
-                    if (half == 0 && dst_user[cb] >= 0) p.blockmax[(int64_t)chunk * p.bm_stride + dst_user[cb]] = v;
-                } else if (half == 0 && u < p.n_r) p.blockmax[sb * p.bm_stride + u] = v;
+                if (half == 0 && u < p.n_r) p.blockmax[sb * p.bm_stride + u] = v;
                 bm[cb] = -INFINITY;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accB[cb][r] = -INFINITY;        // the deferred epilogue becomes a no-op
             }
         }
         if (t + 1 < n_tiles) {
@@ -327,13 +251,13 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
 // stores user blocks 2g, 2g + 1.  The partial sums of a score are added in a different order than in the 32x32x16 kernels:
 // this form serves the FILTERS only (K2f / K2c: their bound charges every addition of the chain, in any order); the plain
 // bf16 two-stage top-k, whose stage 3 must reproduce stage 1's maxima bit for bit, keeps the 32x32x16 kernel.
-// GRP: the grouped launch of the cascade (one superblock per workgroup, rows through row_index), as in blockmax_pipe_kernel.
-// NUB: 16-user blocks per wave (8: 128 users, 512 per workgroup, 2 workgroups per CU; 4: 64 users, 256 per workgroup, 3 per CU --
-// the grouped form's alternative: its workgroups start with a dependent gather of their user rows, and more of them in flight
-// hide more of that latency, at twice the item-tile reads per flop)
-// RDL: the step's LDS operand prefetch is issued AFTER its MFMAs (true) instead of before (false, the default): the change
-// that gave the int8 kernel 3% (score_blockmax_i8.hip) measured slightly SLOWER here (dense 151.5 vs 150.5 ms, grouped 6.79 vs
-// 6.74: 8 user blocks and 4 k-steps per block leave the drain less exposed); kept as tuning blockmax_bf16_rdlate = 1.
+// GRP: the grouped launch of the cascade (one superblock per workgroup, rows through row_index): stage 2 of the int8 cascade,
+// the refined entries of the table the int8 stage wrote.
+// Tried and measured slower at 1M x 1M, and deleted: 4 user blocks per wave in the grouped launch (256 users per workgroup,
+// 3 per CU: more workgroups in flight to hide the dependent gather of their user rows, at twice the item-tile reads per flop)
+// 6.98 against 6.82 ms; the step's LDS operand prefetch AFTER its MFMAs instead of before -- the change that gave the int8
+// kernel 3% (score_blockmax_i8.hip) -- dense 151.5 against 150.5 ms, grouped 6.79 against 6.74 (8 user blocks and 4 k-steps per
+// block leave the drain less exposed).
 // LIST (the cascade's refining launches, csrc/topk_candidates.hip): besides the maxima, every ITEM whose bf16 score reaches the
 // user's provisional floor p.cand_floor[u] is appended to the user's candidate list (p.cand[u][slot], slot from an atomic on
 // p.cand_n[u]).  In the MFMA loop that costs one v_max3 + v_max + v_cmp per 4-item accumulator; a lane whose four scores hold a
@@ -341,6 +265,7 @@ __global__ __launch_bounds__(256, WPS) void blockmax_pipe_kernel(ScoreParams p)
 // atomics, no waiting); the queue is emptied -- scores + user bias compared exactly, atomics, 8-byte stores -- at the end of
 // the superblock, and inside it only if it runs more than LQ_FLUSH entries full: then the 256 entries half a block step can add
 // always fit (popular items of fitted catalogues hit for every user of the wave at once), so no hit is ever dropped.
+constexpr int NUB = 8;                    // 16-user blocks per wave: 128 users, 512 per workgroup, 2 workgroups per CU
 constexpr int LQ_CAP = 448;               // queue entries per wave (20 bytes each: 35,840 bytes per workgroup)
 constexpr int LQ_FLUSH = 192;             // a queue fuller than this is emptied before the next half block step (192 + 4 * 64 <= 448)
 
@@ -354,8 +279,8 @@ constexpr int REFINE_DIAG_WGS = 1 << 17;
 __device__ unsigned long long g_refine_clk[(size_t)REFINE_DIAG_WGS * 4];      // per workgroup of the LAST launch: prologue, tile loop, superblock end, whole life
 #endif
 
-template <int KT, bool BIAS, bool GRP, int NUB = 8, bool RDL = false, bool LIST = false>
-__global__ __launch_bounds__(256, NUB == 8 ? 2 : 3) void blockmax_bf16x16_kernel(ScoreParams p)
+template <int KT, bool BIAS, bool GRP, bool LIST = false>
+__global__ __launch_bounds__(256, 2) void blockmax_bf16x16_kernel(ScoreParams p)
 {
 #ifdef TREC_CAND_DIAG
     const unsigned long long dg_t0 = wall_clock64();
@@ -477,7 +402,7 @@ __global__ __launch_bounds__(256, NUB == 8 ? 2 : 3) void blockmax_bf16x16_kernel
     }
     if (LIST && !GRP) {
         // the dense listing launch over the HOT superblocks (trec_score_gemm_refine_candidates_hot): a user whose entry of this
-        // superblock is -inf was listed for it by the pre-refining launch already (trec_topk_prerefine_tau marked it) -- it sits
+        // superblock is -inf was listed for it by the pre-refining launch already (which marked the entry itself: p.pre_max) -- it sits
         // this superblock out (no second copy of its candidates in its 128 slots, the saved maximum stays where it is)
         float mk[NRI];
 #pragma unroll
@@ -632,22 +557,18 @@ __global__ __launch_bounds__(256, NUB == 8 ? 2 : 3) void blockmax_bf16x16_kernel
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
             const int blk = s / KS, ks = s % KS;
-            if (!RDL && s + 2 < NSTEP)
+            if (s + 2 < NSTEP)
                 tf[(s + 2) % 3] = *(const bf16x8*)(tb + ((s + 2) / KS) * 16 * RB + koff[(s + 2) % KS]);
             if (ks == 0) {
 #pragma unroll
                 for (int ub = 0; ub < NUB; ++ub)
                     acc[ub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf[s % 3], rfb[ub][0], c0, 0, 0, 0);
-                if (RDL) __builtin_amdgcn_sched_barrier(0);
                 if (BIAS && blk + 1 < NBLK) c0 = *(const f32x4*)(sd + 16 * (blk + 1));      // lands under this block's MFMAs
             } else {
 #pragma unroll
                 for (int ub = 0; ub < NUB; ++ub)
                     acc[ub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf[s % 3], rfb[ub][ks], acc[ub], 0, 0, 0);
-                if (RDL) __builtin_amdgcn_sched_barrier(0);
             }
-            if (RDL && s + 2 < NSTEP)
-                tf[(s + 2) % 3] = *(const bf16x8*)(tb + ((s + 2) / KS) * 16 * RB + koff[(s + 2) % KS]);
             if (ks == KS - 1 && !LIST) {
 #pragma unroll
                 for (int ub = 0; ub < NUB; ++ub) {
@@ -775,12 +696,12 @@ __global__ __launch_bounds__(256, NUB == 8 ? 2 : 3) void blockmax_bf16x16_kernel
 #endif
 }
 
-template <int KT, bool BIAS, bool GRP, int NUB = 8, bool RDL = false, bool LIST = false>
+template <int KT, bool BIAS, bool GRP, bool LIST = false>
 int launch_bf16x16(ScoreParams p, hipStream_t st)
 {
     constexpr int LDS = 2 * BN * KT * 2 + 2 * BN * 4 + (LIST ? 4 * LQ_CAP * 20 + 4 * 4 * NUB * 16 * 4 : 0);
     constexpr int RW = 4 * NUB * 16;
-    auto kern = blockmax_bf16x16_kernel<KT, BIAS, GRP, NUB, RDL, LIST>;
+    auto kern = blockmax_bf16x16_kernel<KT, BIAS, GRP, LIST>;
     static bool attr_set = false;
     if (!attr_set && LDS > 32 * 1024) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -969,74 +890,36 @@ int launch_f32(ScoreParams p, int sb_rows, hipStream_t st)
     return trec_check_launch("trec_score_gemm_blockmax (pipelined fp32)");
 }
 
-template <int KT, bool BIAS, int NCB, int WPS, bool OVL, int NBUF>
-int launch_one_nbuf(ScoreParams p, hipStream_t st)
+template <int KT, bool BIAS>
+int launch_one(ScoreParams p, hipStream_t st)
 {
-    constexpr int LDS = NBUF * BN * KT * 2 + NBUF * BN * 4;
-    auto kern = blockmax_pipe_kernel<KT, BIAS, NCB, WPS, OVL, NBUF>;
+    constexpr int LDS = 2 * BN * KT * 2 + 2 * BN * 4;
+    auto kern = blockmax_pipe_kernel<KT, BIAS>;
     static bool attr_set = false;
     if (!attr_set && LDS > 32 * 1024) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_set = true;
     }
-    p.n_rblocks = (int)ceil_div64(p.n_r, 4 * NCB * 32);
+    p.n_rblocks = (int)ceil_div64(p.n_r, 4 * 4 * 32);
     const unsigned blocks = (unsigned)p.n_rblocks * (unsigned)p.n_chunks;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), LDS, st, p);
     return trec_check_launch("trec_score_gemm_blockmax (pipelined)");
 }
 
-// Two LDS buffers by default; "blockmax_nbuf" = 3 selects the triple-buffered form.  Measured on one box, 1M x 1M x 128,
-// biased (profiles/r02_stage1_ab.txt): round-1 kernel 165.7 ms | 2 buffers with the bias row through global_load_lds
-// (no staging register, no commit store) 164.6 ms | 3 buffers 166.7 ms -- a tile's loads already land within one tile of
-// MFMAs; the third buffer only costs LDS.
-template <int KT, bool BIAS, int NCB, int WPS, bool OVL = true>
-int launch_one(ScoreParams p, hipStream_t st)
-{
-    if (trec_get_tuning("blockmax_nbuf", 2) == 3) return launch_one_nbuf<KT, BIAS, NCB, WPS, OVL, 3>(p, st);
-    return launch_one_nbuf<KT, BIAS, NCB, WPS, OVL, 2>(p, st);
-}
-
 }  // namespace
 
-// grouped form: p.n_r padded resident rows (a multiple of 512), p.rblock_chunk [n_r / 512], p.row_index [n_r],
-// p.chunk_len = the superblock height
-template <int KT, bool BIAS>
-int launch_grouped(ScoreParams p, hipStream_t st)
-{
-    constexpr int LDS = 2 * BN * KT * 2 + 2 * BN * 4;
-    auto kern = blockmax_pipe_kernel<KT, BIAS, 4, 2, false, 2, true>;
-    static bool attr_set = false;
-    if (!attr_set && LDS > 32 * 1024) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    p.n_rblocks = (int)(p.n_r / 512);
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.n_rblocks), dim3(256), LDS, st, p);
-    return trec_check_launch("trec_score_gemm_blockmax_grouped");
-}
-
+// grouped form (stage 2 of the int8 cascade): p.n_r padded resident rows (a multiple of 512), p.row_index [n_r], p.chunk_len =
+// the superblock height; p.rblock_chunk [n_r / 512] = the superblock of each workgroup or, with p.capacity > 0, the
+// superblocks' row counts (the kernel's two layouts).  p.cand: the refining launch that also lists candidates (LIST).
 int launch_blockmax_pipelined_grouped(const ScoreParams& p, int kt, hipStream_t st)
 {
     const bool bias = p.r_bias || p.t_bias;
-    if (trec_get_tuning("blockmax_bf16_mfma16", 1) != 0) {       // the 16x16x32 form (filters only: see blockmax_bf16x16_kernel)
-        // (the 64-users-per-wave A/B form has no LIST instance and decodes workgroup slots in its own units: it only serves the
-        // plain fixed-capacity launch -- with candidate lists or a workgroup map the knob is ignored)
-        if (kt == 128 && p.capacity > 0 && !p.cand && !p.wg_map && trec_get_tuning("cascade_grouped_nub", 8) == 4)
-            return bias ? launch_bf16x16<128, true, true, 4>(p, st) : launch_bf16x16<128, false, true, 4>(p, st);
-        if (p.cand) {                                             // the refining launch that also lists candidates (LIST)
-            if (kt == 128) return bias ? launch_bf16x16<128, true, true, 8, false, true>(p, st) : launch_bf16x16<128, false, true, 8, false, true>(p, st);
-            if (kt == 64) return bias ? launch_bf16x16<64, true, true, 8, false, true>(p, st) : launch_bf16x16<64, false, true, 8, false, true>(p, st);
-        }
-        if (kt == 128 && bias && trec_get_tuning("blockmax_bf16_rdlate", 0) != 0) return launch_bf16x16<128, true, true, 8, true>(p, st);
-        if (kt == 128) return bias ? launch_bf16x16<128, true, true>(p, st) : launch_bf16x16<128, false, true>(p, st);
-        if (kt == 64) return bias ? launch_bf16x16<64, true, true>(p, st) : launch_bf16x16<64, false, true>(p, st);
+    if (p.cand) {
+        if (kt == 128) return bias ? launch_bf16x16<128, true, true, true>(p, st) : launch_bf16x16<128, false, true, true>(p, st);
+        if (kt == 64) return bias ? launch_bf16x16<64, true, true, true>(p, st) : launch_bf16x16<64, false, true, true>(p, st);
     }
-    if (p.capacity > 0) {
-        trec_set_last_error("trec_score_gemm_blockmax_grouped: the fixed-capacity layout needs the 16x16x32 form (tuning blockmax_bf16_mfma16 = 1)");
-        return TREC_ERR_UNSUPPORTED;
-    }
-    if (kt == 128) return bias ? launch_grouped<128, true>(p, st) : launch_grouped<128, false>(p, st);
-    if (kt == 64) return bias ? launch_grouped<64, true>(p, st) : launch_grouped<64, false>(p, st);
+    if (kt == 128) return bias ? launch_bf16x16<128, true, true>(p, st) : launch_bf16x16<128, false, true>(p, st);
+    if (kt == 64) return bias ? launch_bf16x16<64, true, true>(p, st) : launch_bf16x16<64, false, true>(p, st);
     return TREC_ERR_UNSUPPORTED;
 }
 
@@ -1044,13 +927,12 @@ int launch_blockmax_pipelined_grouped(const ScoreParams& p, int kt, hipStream_t 
 // (trec_score_gemm_blockmax_hot) chunk c of the launch is superblock p.rblock_chunk[c] (-1: idle), p.chunk_len = sb_rows.
 int launch_blockmax_filter16(const ScoreParams& p, int kt, hipStream_t st)
 {
-    if (p.euclid || (trec_get_tuning("blockmax_bf16_mfma16", 1) == 0 && !p.rblock_chunk)) return TREC_ERR_UNSUPPORTED;
+    if (p.euclid) return TREC_ERR_UNSUPPORTED;
     const bool bias = p.r_bias || p.t_bias;
     if (p.cand) {
-        if (kt == 128) return bias ? launch_bf16x16<128, true, false, 8, false, true>(p, st) : launch_bf16x16<128, false, false, 8, false, true>(p, st);
-        if (kt == 64) return bias ? launch_bf16x16<64, true, false, 8, false, true>(p, st) : launch_bf16x16<64, false, false, 8, false, true>(p, st);
+        if (kt == 128) return bias ? launch_bf16x16<128, true, false, true>(p, st) : launch_bf16x16<128, false, false, true>(p, st);
+        if (kt == 64) return bias ? launch_bf16x16<64, true, false, true>(p, st) : launch_bf16x16<64, false, false, true>(p, st);
     }
-    if (kt == 128 && bias && trec_get_tuning("blockmax_bf16_rdlate", 0) != 0) return launch_bf16x16<128, true, false, 8, true>(p, st);
     if (kt == 128) return bias ? launch_bf16x16<128, true, false>(p, st) : launch_bf16x16<128, false, false>(p, st);
     if (kt == 64) return bias ? launch_bf16x16<64, true, false>(p, st) : launch_bf16x16<64, false, false>(p, st);
     return TREC_ERR_UNSUPPORTED;
@@ -1060,16 +942,8 @@ int launch_blockmax_pipelined(const ScoreParams& p, int kt, hipStream_t st)
 {
     if (p.euclid) return TREC_ERR_UNSUPPORTED;
     const bool bias = p.r_bias || p.t_bias;
-    // users per wave / accumulator sets / workgroups per CU, measured at 1M x 1M x 128, biased (profiles/r01_k2_ablation.txt):
-    //   5 (default): 128 users, one set,  2/CU  1528 TF      3:  96 users, one set,  2/CU  1468 TF
-    //   2:            64 users, two sets, 2/CU  1290-1340 TF  4: 128 users, two sets, 1/CU  1257 TF
-    const int shape = trec_get_tuning("blockmax_shape", 5);
-    if (kt == 128 && shape == 3) return bias ? launch_one<128, true, 3, 2, false>(p, st) : launch_one<128, false, 3, 2, false>(p, st);
-    if (kt == 128 && shape == 5) return bias ? launch_one<128, true, 4, 2, false>(p, st) : launch_one<128, false, 4, 2, false>(p, st);
-    if (kt == 128 && shape == 4) return bias ? launch_one<128, true, 4, 1>(p, st) : launch_one<128, false, 4, 1>(p, st);
-    if (kt == 128) return bias ? launch_one<128, true, 2, 2>(p, st) : launch_one<128, false, 2, 2>(p, st);
-    if (kt == 64 && shape == 2) return bias ? launch_one<64, true, 2, 3>(p, st) : launch_one<64, false, 2, 3>(p, st);
-    if (kt == 64) return bias ? launch_one<64, true, 4, 2, false>(p, st) : launch_one<64, false, 4, 2, false>(p, st);
+    if (kt == 128) return bias ? launch_one<128, true>(p, st) : launch_one<128, false>(p, st);
+    if (kt == 64) return bias ? launch_one<64, true>(p, st) : launch_one<64, false>(p, st);
     return TREC_ERR_UNSUPPORTED;
 }
 

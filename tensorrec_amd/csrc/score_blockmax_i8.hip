@@ -16,13 +16,9 @@
 // tensorrec/recommendation_graphs.py:80; nothing it computes is returned to the caller -- survivors are re-scored in bf16
 // (bounded again) and finally in fp32, bit-identical to the oracle.
 //
-// Two forms of the kernel: blockmax_i8_kernel on v_mfma_i32_32x32x32_i8 (the first one; tuning blockmax_i8_mfma = 0) and
-// blockmax_i8x16_kernel on v_mfma_i32_16x16x64_i8 (the default: 17% more work per joule at the power cap, see its header).
-// Plan of the first form (K = 128 bytes per row): a wave owns NCB x 32 users whose int8 fragments stay in registers (NCB x 4
-// k-steps x 4 VGPRs); item tiles of 128 rows x 128 B = 16 KB are double-buffered in LDS through global_load_lds with the
-// 16-byte-chunk XOR swizzle of score_gemm.hip; a 32-item block is 4 k-steps of NCB MFMAs fed by ONE ds_read_b128 each; the
-// block's epilogue (8 v_max3_i32 per accumulator) runs right after its last k-step, the next block's bias row is read straight
-// into accumulator 0.  Lane & 31 is the user (acc = mfma(items, users)), exactly the orientation of the bf16 kernel.
+// One kernel, blockmax_i8x16_kernel on v_mfma_i32_16x16x64_i8: 4 waves per workgroup, each with the int8 fragments of its
+// users resident in registers; item tiles of 128 rows x K bytes are double-buffered in LDS through global_load_lds with a
+// 16-byte-chunk XOR swizzle; a 16-item block is K / 64 k-steps of one MFMA per 16-user block, fed by ONE ds_read_b128 each.
 #include "score_common.hpp"
 #include <math.h>
 #include <limits.h>
@@ -31,263 +27,48 @@
 namespace {
 
 typedef int v4i32 __attribute__((ext_vector_type(4)));
-typedef int v16i32 __attribute__((ext_vector_type(16)));
 
-constexpr int BNQ = 128;        // item rows per tile (four 32-row MFMA blocks)
+constexpr int BNQ = 128;        // item rows per tile (eight 16-row MFMA blocks, one barrier per tile)
+constexpr int NWQ = 4;          // waves per workgroup sharing one item tile stream (two workgroups per CU)
 
+// Bare MFMA streams on random operands, ~1 s each at the 1.3 kW cap (scripts/probe/mfma_stream.hip): i8 32x32x32 3.45 Pop/s,
+// i8 16x16x64 4.05 Pop/s (bf16 32x32x16: 1.80 PF).  The 16x16x64 form does the same work per operand byte (a 16-item x 64-k
+// fragment, one ds_read_b128, feeds one MFMA per 16-user block of the wave) and needs half the accumulator
+// registers.  Lane = (k-group g = lane >> 4 of the operands | row-group g of the result, user /
+// item row lane & 15): the maxima of the four row-groups are combined by two shuffles at a superblock end, after which
+// row-group g owns NUB / 4 of the user blocks (their table stores, bound constants and top-k register lists: NUB / 4 x TK
+// registers, not NUB x TK).
+// NUB: 16-user blocks per wave.  12 (192 users: a third fewer LDS reads and tile streams per flop, 78.8 against 81.9 ms at
+// 1M x 1M with the 10-slot lists, profiles/r02_power_trace_i8.txt) unless the 16-slot lists need the registers: then 8.
 // TK > 0: the kernel also keeps, per user, the TK largest LOWER bounds M - e(u, s) of the superblocks of its chunk (sorted
 // registers, one insertion per superblock end) and writes them to chunk_top: the k-th largest over the chunks' lists is
 // tau8 -- no pass over the 7.8 GB table for it.
-template <int KT, bool BIAS, int NCB, int WPS, int TK>
-__global__ __launch_bounds__(256, WPS) void blockmax_i8_kernel(ScoreParams p)
+// A step's LDS operand prefetch (for step s + 2) is issued AFTER the step's MFMAs: the compiler closes every block start with
+// s_waitcnt lgkmcnt(0) -- a full drain, although the operands the MFMAs need were read two steps earlier -- so a prefetch
+// issued right in front of it is waited for at its full LDS latency, once per 24 MFMAs; issued after the MFMAs, the next
+// drain finds it a whole group of max3 old.
+// Tried and measured slower, at 1M x 1M on one box (docs/history/DESIGN_rounds_1_to_5.md), and deleted:
+//   the same stage on v_mfma_i32_32x32x32_i8 (the first form of this kernel): 91-94 ms against 78.8 ms;
+//   8 waves per workgroup (one workgroup per CU), 256-row tiles, the other users-per-wave count: slower each;
+//   the prefetch before the step's MFMAs 78.1 ms, in the middle of them 77.2 ms, after them with the block's max3 pinned
+//   between the MFMAs by sched_group_barrier 75.5 ms -- against 75.7 ms as shipped (two waves per SIMD already cover each
+//   other's max3 phase).
+template <int KT, bool BIAS, int TK, int NUB>
+__global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(ScoreParams p)
 {
-    constexpr int RB = KT;                   // bytes per operand row
-    constexpr int CH = RB / 16;              // 16-byte chunks per row (8 at K = 128)
-    constexpr int KS = KT / 32;              // MFMA k-steps per block
-    constexpr int TILE_BYTES = BNQ * RB;
-    constexpr int NSLOT = BNQ * CH / 256;    // 16-byte staging slots per thread per tile
-    constexpr int NBLK = BNQ / 32;
-    constexpr int NSTEP = NBLK * KS;
-    static_assert(KT == 64 || KT == 128 || KT == 256, "int8 BLOCKMAX covers K = 64 / 128 / 256");
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];    // [2][TILE_BYTES] item tiles | [2][BNQ] integer item biases
-    int* side = (int*)(smem + 2 * TILE_BYTES);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
-    const int rblock = blockIdx.x % p.n_rblocks;
-    const int chunk = blockIdx.x / p.n_rblocks;
-    const int64_t r_base = ((int64_t)rblock * 4 + wave) * (NCB * 32);
-    const int64_t t_begin = (int64_t)chunk * p.chunk_len;
-    const int64_t t_end = (t_begin + p.chunk_len < p.n_t) ? t_begin + p.chunk_len : p.n_t;
-    const int n_tiles = (int)((t_end - t_begin + BNQ - 1) / BNQ);
-
-    // ---- resident user fragments: lane holds k = 32 ks + 16 half + 0..15 of its user ----
-    v4i32 rfq[NCB][KS];
-    float r_bias[NCB];
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-        int64_t row = r_base + cb * 32 + l31;
-        if (row >= p.n_r) row = p.n_r - 1;                       // clamped rows are never written
-        const char* src = (const char*)p.R + row * (int64_t)RB;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) rfq[cb][ks] = *(const v4i32*)(src + (ks * 2 + half) * 16);
-        r_bias[cb] = (BIAS && p.r_bias) ? p.r_bias[row] : 0.f;
-    }
-
-    // ---- staging: slot q = i*256 + tid -> (row, physical chunk); source offsets fixed per thread ----
-    int slot_off[NSLOT];
-#pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
-        const int q = i * 256 + tid;
-        const int row = q / CH, pc = q % CH;
-        const int sw = CH >= 16 ? (row & 15) : (CH == 8 ? ((row >> 1) & 7) : ((row >> 2) & 3));
-        slot_off[i] = row * RB + ((pc ^ sw) * 16);
-    }
-    const char* t_chunk = (const char*)p.T + t_begin * (int64_t)RB;
-    // integer item biases (units of the scale product): one table per user scale class
-    const int* t_bias_q = p.t_bias ? (const int*)p.t_bias + (p.wg_class ? (int64_t)p.wg_class[rblock] * p.bias_stride : 0) : nullptr;
-    auto stage_issue = [&](int tile, int buf) {
-        const int64_t row0 = t_begin + (int64_t)tile * BNQ;
-        const bool clamp = row0 + BNQ > p.n_t;                   // wave-uniform: only the very last tile
-        if (BIAS && wave < 2) {                                  // 128 bias words: waves 0 and 1, one 4-byte-per-lane DMA each
-            int64_t g = row0 + wave * 64 + lane;
-            if (g >= p.n_t) g = p.n_t - 1;                       // duplicate of the last valid item: max unchanged
-            if (t_bias_q) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(t_bias_q + g),
-                                                 (__attribute__((address_space(3))) void*)(side + buf * BNQ + wave * 64), 4, 0, 0);
-            } else {
-                side[buf * BNQ + wave * 64 + lane] = 0;
-            }
-        }
-        const char* tile_base = t_chunk + (int64_t)tile * (BNQ * RB);
-#pragma unroll
-        for (int i = 0; i < NSLOT; ++i) {
-            int off = slot_off[i];
-            if (clamp) {
-                const int last = (int)(p.n_t - 1 - row0);
-                const int row = (i * 256 + tid) / CH;
-                if (row > last) off -= (row - last) * RB;
-            }
-            char* dst = smem + buf * TILE_BYTES + (i * 256 + wave * 64) * 16;       // wave-uniform; lane*16 is implicit
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tile_base + off),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        }
-    };
-
-    // per-lane LDS offsets of the KS operand chunks of "my" item row inside a 32-row block
-    int koff[KS];
-    {
-        const int sw = CH >= 16 ? (l31 & 15) : (CH == 8 ? ((l31 >> 1) & 7) : ((l31 >> 2) & 3));
-        // rows l31 + 32 j have the same swizzle: 32 j leaves (row & 15), ((row >> 1) & 7) and ((row >> 2) & 3) alone
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) koff[ks] = l31 * RB + (((ks * 2 + half) ^ sw) * 16);
-    }
-
-    v16i32 acc[NCB];
-    int bm[NCB];
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) bm[cb] = INT_MIN;
-    float top[TK ? NCB : 1][TK ? TK : 1];
-    float e_nx[TK ? NCB : 1], e_ex[TK ? NCB : 1], e_cu[TK ? NCB : 1];
-    if (TK) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            int64_t row = r_base + cb * 32 + l31;
-            if (row >= p.n_r) row = p.n_r - 1;
-            e_nx[cb] = p.r_err[row * 4]; e_ex[cb] = p.r_err[row * 4 + 1]; e_cu[cb] = p.r_err[row * 4 + 2];
-#pragma unroll
-            for (int j = 0; j < TK; ++j) top[cb][j] = -INFINITY;
-        }
-    }
-
-    auto read_c0 = [&](v16i32& c, const int* sdi) {           // integer item biases of the block's 16 rows of this half-wave
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const v4i32 tb4 = *(const v4i32*)(sdi + 8 * q);
-            c[4 * q] = tb4[0]; c[4 * q + 1] = tb4[1]; c[4 * q + 2] = tb4[2]; c[4 * q + 3] = tb4[3];
-        }
-    };
-
-    auto tile_body = [&](auto bufc) __attribute__((always_inline)) {
-        constexpr int buf = decltype(bufc)::value;
-        const char* tb = smem + buf * TILE_BYTES;
-        const int* sd = side + buf * BNQ + 4 * half;
-        v4i32 tf[3];
-        if (BIAS) read_c0(acc[0], sd);
-        tf[0] = *(const v4i32*)(tb + koff[0]);
-        tf[1] = *(const v4i32*)(tb + (KS > 1 ? koff[1 % KS] : 32 * RB + koff[0]));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < NSTEP; ++s) {
-            const int blk = s / KS, ks = s % KS;
-            if (s + 2 < NSTEP)
-                tf[(s + 2) % 3] = *(const v4i32*)(tb + ((s + 2) / KS) * 32 * RB + koff[(s + 2) % KS]);
-            if (ks == 0) {
-                if (BIAS) {
-#pragma unroll
-                    for (int cb = NCB - 1; cb >= 0; --cb)
-                        acc[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(tf[s % 3], rfq[cb][0], acc[0], 0, 0, 0);
-                } else {
-                    const v16i32 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                    for (int cb = 0; cb < NCB; ++cb)
-                        acc[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(tf[s % 3], rfq[cb][0], z, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb)
-                    acc[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(tf[s % 3], rfq[cb][ks], acc[cb], 0, 0, 0);
-            }
-            if (ks == KS - 1) {
-                // block epilogue: accumulator 0 first, then it takes the next block's bias row while the others finish
-#pragma unroll
-                for (int j = 0; j < 8; ++j) bm[0] = max(max(bm[0], acc[0][2 * j]), acc[0][2 * j + 1]);
-                if (BIAS && blk + 1 < NBLK) read_c0(acc[0], sd + 32 * (blk + 1));
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-#pragma unroll
-                    for (int cb = 1; cb < NCB; ++cb) bm[cb] = max(max(bm[cb], acc[cb][2 * j]), acc[cb][2 * j + 1]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    stage_issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // integer score units -> float: a_user * (item scale of the superblock); a_user = the scale of this workgroup's users
-    const float a_user = p.wg_scale ? p.wg_scale[rblock] : p.scales[0];
-    // the NEXT superblock's statistics are fetched while the first tile of the current one is computed: issued at a
-    // superblock end they would sit, fresh, in front of the s_waitcnt vmcnt(0) that closes every tile
-    const int64_t sb0 = t_begin / ((int64_t)p.sb_tiles * BNQ);
-    f32x4 ss_cur = *(const f32x4*)(p.sb_stats + sb0 * 4), ss_next = ss_cur;
-    for (int t = 0; t < n_tiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < n_tiles) stage_issue(t + 1, buf ^ 1);
-        if ((t % p.sb_tiles) == 0 && t + p.sb_tiles < n_tiles)
-            ss_next = *(const f32x4*)(p.sb_stats + (sb0 + t / p.sb_tiles + 1) * 4);
-        if (buf == 0) tile_body(std::integral_constant<int, 0>{});
-        else tile_body(std::integral_constant<int, 1>{});
-
-        if (((t + 1) % p.sb_tiles) == 0 || t + 1 == n_tiles) {
-            // end of a superblock: combine the two half-wave maxima of each user, convert, add the user bias, store, reset
-            const int64_t sb = sb0 + t / p.sb_tiles;
-            const float scale = a_user * ss_cur[0];
-            const float yh = TK ? ss_cur[1] : 0.f, dy = TK ? ss_cur[2] : 0.f, db = TK ? a_user * ss_cur[3] : 0.f;
-            ss_cur = ss_next;
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const int o = __shfl_xor(bm[cb], 32, 64);
-                const int m = bm[cb] > o ? bm[cb] : o;
-                float v = (float)m * scale;                   // (exact below 2^24; beyond it one rounding, charged in i8_pair_err)
-                if (BIAS) v = v + r_bias[cb];
-                const int64_t u = r_base + cb * 32 + l31;
-                if (half == 0 && u < p.n_r) p.blockmax[sb * p.bm_stride + u] = v;
-                bm[cb] = INT_MIN;
-                if (TK) {
-                    float lb = v - i8_pair_err(e_nx[cb], e_ex[cb], e_cu[cb], yh, dy, db, KT);
-                    lb = (lb == lb) ? lb : -INFINITY;          // a NaN certifies nothing
-                    if (p.top_tag) lb = lb_tag(lb, t / p.sb_tiles);      // (uniform) the superblock's index inside this chunk
-                    // sorted insertion into a descending list, one v_med3 per slot: new t_j = median(t_j, t_{j-1}, lb)
-                    // (lb <= t_j: t_j stays | t_j < lb <= t_{j-1}: lb lands here | lb > t_{j-1}: t_{j-1} moves down)
-#pragma unroll
-                    for (int j = TK - 1; j >= 1; --j) top[cb][j] = __builtin_amdgcn_fmed3f(top[cb][j], top[cb][j - 1], lb);
-                    top[cb][0] = fmaxf(top[cb][0], lb);
-                }
-            }
-        }
-        if (t + 1 < n_tiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    if (TK) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int64_t u = r_base + cb * 32 + l31;
-            if (half == 0 && u < p.n_r) {
-#pragma unroll
-                for (int j = 0; j < TK; ++j) p.chunk_top[((int64_t)chunk * TK + j) * p.bm_stride + u] = top[cb][j];
-            }
-        }
-    }
-}
-
-// ---- the same stage on v_mfma_i32_16x16x64_i8 ------------------------------------------------------------------------
-// Bare MFMA streams on random operands, ~1 s each at the 1.3 kW cap (scripts/probe/mfma_stream.hip): i8 32x32x32 3.45 Pop/s,
-// i8 16x16x64 4.05 Pop/s (bf16 32x32x16: 1.80 PF).  The 16x16x64 form does the same work per operand byte (a 16-item x 64-k
-// fragment, one ds_read_b128, feeds 8 MFMAs of 16 users each = the 128 users of a wave) and needs half the accumulator
-// registers (8 x 4).  Lane = (k-group g = lane >> 4 of the operands | row-group g of the result, user / item row lane & 15):
-// the maxima of the four row-groups are combined by two shuffles at a superblock end, after which row-group g owns NUB / 4
-// of the user blocks (their table stores, bound constants and top-k register lists: NUB / 4 x TK registers, not NUB x TK).
-// NUB: 16-user blocks per wave (8: 128 users, 12: 192 users); NW: waves per workgroup sharing one item tile stream (4: two
-// workgroups per CU, 8: one)
-// BT: item rows per tile (one barrier per tile)
-// RDL: where a step's LDS operand prefetch (for step s + 2) sits.  0: before the step's MFMAs (the first form).  The
-// compiler closes every block start with s_waitcnt lgkmcnt(0) -- a full drain, although the operands the MFMAs need were
-// read two steps earlier -- so the prefetch issued right in front of it is waited for at its full LDS latency, once per 24
-// MFMAs.  1 (default): the prefetch is issued AFTER the step's MFMAs, so the next drain finds it a whole group of max3 old:
-// 78.1 -> 75.7 ms at 1M x 1M on one box (0.656 -> 0.677 of 5 Pop/s).  2: in the middle of the MFMAs (77.2).  3: after them,
-// with the block's max3 interleaved between the MFMAs by sched_group_barrier (75.5: the same -- two waves per SIMD already
-// cover each other's max3 phase).
-template <int KT, bool BIAS, int TK, int NUB, int NW, int BT, int RDL = 1>
-__global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScoreParams p)
-{
-    constexpr int NT = NW * 64;              // threads per workgroup
+    constexpr int NT = NWQ * 64;              // threads per workgroup
     constexpr int OW = NUB / 4;              // user blocks a row-group owns at superblock ends
     static_assert(NUB % 4 == 0, "user blocks per wave must split over the four row-groups");
     constexpr int RB = KT;                   // bytes per operand row
     constexpr int CH = RB / 16;              // 16-byte chunks per row (8 at K = 128, 4 at K = 64)
     constexpr int KS = KT / 64;              // MFMA k-steps per block
-    constexpr int TILE_BYTES = BT * RB;
-    constexpr int NSLOT = BT * CH / NT;
-    constexpr int NBLK = BT / 16;           // 16-item blocks per tile
+    constexpr int TILE_BYTES = BNQ * RB;
+    constexpr int NSLOT = BNQ * CH / NT;
+    constexpr int NBLK = BNQ / 16;           // 16-item blocks per tile
     constexpr int NSTEP = NBLK * KS;
     static_assert(KT == 64 || KT == 128, "int8 16x16x64 BLOCKMAX covers K = 64 / 128");
 
-    extern __shared__ __attribute__((aligned(16))) char smem[];    // [2][TILE_BYTES] item tiles | [2][BT] integer item biases
+    extern __shared__ __attribute__((aligned(16))) char smem[];    // [2][TILE_BYTES] item tiles | [2][BNQ] integer item biases
     int* side = (int*)(smem + 2 * TILE_BYTES);
 
     const int tid = threadIdx.x;
@@ -299,10 +80,10 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
     // an idle workgroup (trec_user_prep_sorted sizes the user layout by a bound the host knows; the workgroups beyond the padded
     // row count carry scale 0): nothing to compute, nothing written -- its users' thresholds are +inf
     if (p.wg_scale && p.wg_scale[rblock] == 0.f) return;
-    const int64_t r_base = ((int64_t)rblock * NW + wave) * (NUB * 16);
+    const int64_t r_base = ((int64_t)rblock * NWQ + wave) * (NUB * 16);
     const int64_t t_begin = (int64_t)chunk * p.chunk_len;
     const int64_t t_end = (t_begin + p.chunk_len < p.n_t) ? t_begin + p.chunk_len : p.n_t;
-    const int n_tiles = (int)((t_end - t_begin + BT - 1) / BT);
+    const int n_tiles = (int)((t_end - t_begin + BNQ - 1) / BNQ);
     // physical 16-byte chunk = logical chunk ^ swz(row): 8 consecutive rows of one logical chunk (what 8 consecutive lanes
     // read) land on 8 distinct chunk positions = all 32 banks
     auto swz = [](int row) { return CH == 8 ? (row & 7) : ((row >> 1) & 3); };
@@ -343,19 +124,19 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
     const char* t_chunk = (const char*)p.T + t_begin * (int64_t)RB;
     const int* t_bias_q = p.t_bias ? (const int*)p.t_bias + (p.wg_class ? (int64_t)p.wg_class[rblock] * p.bias_stride : 0) : nullptr;
     auto stage_issue = [&](int tile, int buf) {
-        const int64_t row0 = t_begin + (int64_t)tile * BT;
-        const bool clamp = row0 + BT > p.n_t;                   // wave-uniform: only the very last tile
-        if (BIAS && wave < BT / 64) {
+        const int64_t row0 = t_begin + (int64_t)tile * BNQ;
+        const bool clamp = row0 + BNQ > p.n_t;                   // wave-uniform: only the very last tile
+        if (BIAS && wave < BNQ / 64) {
             int64_t gi = row0 + wave * 64 + lane;
             if (gi >= p.n_t) gi = p.n_t - 1;                     // duplicate of the last valid item: max unchanged
             if (t_bias_q) {
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(t_bias_q + gi),
-                                                 (__attribute__((address_space(3))) void*)(side + buf * BT + wave * 64), 4, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)(side + buf * BNQ + wave * 64), 4, 0, 0);
             } else {
-                side[buf * BT + wave * 64 + lane] = 0;
+                side[buf * BNQ + wave * 64 + lane] = 0;
             }
         }
-        const char* tile_base = t_chunk + (int64_t)tile * (BT * RB);
+        const char* tile_base = t_chunk + (int64_t)tile * (BNQ * RB);
 #pragma unroll
         for (int i = 0; i < NSLOT; ++i) {
             int off = slot_off[i];
@@ -383,7 +164,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
     auto tile_body = [&](auto bufc) __attribute__((always_inline)) {
         constexpr int buf = decltype(bufc)::value;
         const char* tb = smem + buf * TILE_BYTES;
-        const int* sd = side + buf * BT + 4 * g;                // the block's integer biases of result rows 4 g .. 4 g + 3
+        const int* sd = side + buf * BNQ + 4 * g;                // the block's integer biases of result rows 4 g .. 4 g + 3
         v4i32 tf[3];
         v4i32 c0 = {0, 0, 0, 0};
         if (BIAS) c0 = *(const v4i32*)sd;
@@ -393,49 +174,25 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
             const int blk = s / KS, ks = s % KS;
-            auto prefetch = [&]() {
-                if (s + 2 < NSTEP) tf[(s + 2) % 3] = *(const v4i32*)(tb + ((s + 2) / KS) * 16 * RB + koff[(s + 2) % KS]);
-            };
-            if (RDL == 0) prefetch();
             if (ks == 0) {
 #pragma unroll
-                for (int ub = 0; ub < NUB; ++ub) {
+                for (int ub = 0; ub < NUB; ++ub)
                     acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 3], rfq[ub][0], c0, 0, 0, 0);
-                    if (RDL == 2 && ub == NUB / 2 - 1) { __builtin_amdgcn_sched_barrier(0); prefetch(); __builtin_amdgcn_sched_barrier(0); }
-                }
-                if (RDL == 1) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 if (BIAS && blk + 1 < NBLK) c0 = *(const v4i32*)(sd + 16 * (blk + 1));     // lands under this block's MFMAs
             } else {
 #pragma unroll
-                for (int ub = 0; ub < NUB; ++ub) {
+                for (int ub = 0; ub < NUB; ++ub)
                     acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 3], rfq[ub][ks], acc[ub], 0, 0, 0);
-                    if (RDL == 2 && ub == NUB / 2 - 1) { __builtin_amdgcn_sched_barrier(0); prefetch(); __builtin_amdgcn_sched_barrier(0); }
-                }
-                if (RDL == 1) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if (RDL == 1 || RDL == 3) prefetch();
+            // the operand prefetch for step s + 2, behind this step's MFMAs (see the header)
+            if (s + 2 < NSTEP) tf[(s + 2) % 3] = *(const v4i32*)(tb + ((s + 2) / KS) * 16 * RB + koff[(s + 2) % KS]);
             if (ks == KS - 1) {
 #pragma unroll
                 for (int ub = 0; ub < NUB; ++ub) {
                     bm[ub] = max(max(bm[ub], acc[ub][0]), acc[ub][1]);
                     bm[ub] = max(max(bm[ub], acc[ub][2]), acc[ub][3]);
-                }
-            }
-            if (RDL == 3) {
-                // pin the order inside the step: 3 MFMAs ahead, then (2 max3, 1 MFMA) pairs, the prefetch read in the middle
-                if (ks == KS - 1) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-#pragma unroll
-                    for (int i = 0; i < NUB - 3; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i == (NUB - 3) / 2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-                } else {
-                    __builtin_amdgcn_sched_group_barrier(0x008, NUB / 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, NUB - NUB / 2, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -447,7 +204,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
     __syncthreads();
 
     const float a_user = p.wg_scale ? p.wg_scale[rblock] : p.scales[0];      // the scale of this workgroup's users
-    const int64_t sb0 = t_begin / ((int64_t)p.sb_tiles * BT);
+    const int64_t sb0 = t_begin / ((int64_t)p.sb_tiles * BNQ);
     f32x4 ss_cur = *(const f32x4*)(p.sb_stats + sb0 * 4), ss_next = ss_cur;
     for (int t = 0; t < n_tiles; ++t) {
         const int buf = t & 1;
@@ -502,38 +259,30 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void blockmax_i8x16_kernel(ScorePa
     }
 }
 
-template <int KT, bool BIAS, int TK, int NUB, int NW, int BT, int RDL = 1>
+template <int KT, bool BIAS, int TK, int NUB>
 int launch_i8x16(ScoreParams p, int sb_rows, hipStream_t st)
 {
-    constexpr int LDS = 2 * BT * KT + 2 * BT * 4;
-    auto kern = blockmax_i8x16_kernel<KT, BIAS, TK, NUB, NW, BT, RDL>;
+    constexpr int LDS = 2 * BNQ * KT + 2 * BNQ * 4;
+    auto kern = blockmax_i8x16_kernel<KT, BIAS, TK, NUB>;
     static bool attr_set = false;
     if (!attr_set && LDS > 32 * 1024) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_set = true;
     }
-    p.n_rblocks = (int)ceil_div64(p.n_r, NW * NUB * 16);
-    p.sb_tiles = sb_rows / BT;
+    p.n_rblocks = (int)ceil_div64(p.n_r, NWQ * NUB * 16);
+    p.sb_tiles = sb_rows / BNQ;
     const unsigned blocks = (unsigned)p.n_rblocks * (unsigned)p.n_chunks;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NW * 64), LDS, st, p);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NWQ * 64), LDS, st, p);
     return trec_check_launch("trec_score_gemm_blockmax_i8 (16x16x64)");
 }
 
-template <int KT, bool BIAS, int NCB, int WPS, int TK>
-int launch_i8(ScoreParams p, int sb_rows, hipStream_t st)
+// (list slots, 16-user blocks per wave) = (0, 12), (10, 12) or (16, 8); with K in {64, 128} x bias: 12 instances in all
+template <int KT, bool BIAS>
+int launch_i8x16_lists(const ScoreParams& p, int sb_rows, hipStream_t st)
 {
-    constexpr int LDS = 2 * BNQ * KT + 2 * BNQ * 4;
-    auto kern = blockmax_i8_kernel<KT, BIAS, NCB, WPS, TK>;
-    static bool attr_set = false;
-    if (!attr_set && LDS > 32 * 1024) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    p.n_rblocks = (int)ceil_div64(p.n_r, 4 * NCB * 32);
-    p.sb_tiles = sb_rows / BNQ;
-    const unsigned blocks = (unsigned)p.n_rblocks * (unsigned)p.n_chunks;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), LDS, st, p);
-    return trec_check_launch("trec_score_gemm_blockmax_i8");
+    if (p.top_k == 0) return launch_i8x16<KT, BIAS, 0, 12>(p, sb_rows, st);
+    if (p.top_k == 10) return launch_i8x16<KT, BIAS, 10, 12>(p, sb_rows, st);
+    return launch_i8x16<KT, BIAS, 16, 8>(p, sb_rows, st);
 }
 
 // fp32 rows -> int8 rows [n, kpad] (zero padded), q = clamp(rint(x / scale), +-127), + what the bound needs per row:
@@ -909,13 +658,11 @@ extern "C" int trec_score_bias_i8_classes(const float* bias, int64_t n, int32_t 
     return trec_check_launch("trec_score_bias_i8_classes");
 }
 
-// rows of users one int8 workgroup covers under the current tuning (the granularity of a scale class boundary)
+// rows of users one int8 workgroup covers (the granularity of a scale class boundary): 4 waves of 192 users with the 10-slot
+// lists (and without lists), of 128 users with the 16-slot lists
 extern "C" int32_t trec_score_blockmax_i8_rows_per_workgroup(int32_t top_k)
 {
-    if (trec_get_tuning("blockmax_i8_mfma", 1) == 0) return 4 * 4 * 32;
-    const int waves = trec_get_tuning("blockmax_i8_waves", 4) == 8 ? 8 : 4;
-    const int users = trec_get_tuning("blockmax_i8_users", top_k > 10 ? 128 : 192) == 192 ? 192 : 128;
-    return waves * users;
+    return top_k <= 10 ? NWQ * 12 * 16 : NWQ * 8 * 16;
 }
 
 // r_err [n_users][4] = the users' part of the int8 bound ({||x||, ||x - a q||, ck (|b_u| + gstats[2]), a_u}); gstats[2] = max |item
@@ -950,9 +697,9 @@ extern "C" int trec_score_gemm_blockmax_i8(const void* users_q, const void* item
     const int top_tag = (top_k & 0x100) ? 1 : 0;
     top_k &= 0xff;
     // wg_rows (with wg_scale): the rows per workgroup the caller laid the users out for -- the scales and bias tables are
-    // indexed by workgroup, so a tuning changed between preparation and launch must fail loudly, not shift them
-    TREC_REQUIRE(!wg_scale || wg_rows == trec_score_blockmax_i8_rows_per_workgroup(top_k ? top_k : 10),
-                 "trec_score_gemm_blockmax_i8: the user operand was laid out for another workgroup height (tuning changed since the preparation?)");
+    // indexed by workgroup, so an operand prepared for the other list length must fail loudly, not shift them
+    TREC_REQUIRE(!wg_scale || wg_rows == trec_score_blockmax_i8_rows_per_workgroup(top_k),
+                 "trec_score_gemm_blockmax_i8: the user operand was laid out for another workgroup height (prepared for the other top_k?)");
     TREC_REQUIRE(users_q && items_q && (scales || wg_scale) && sb_stats && blockmax && bm_stride >= n_users, "trec_score_gemm_blockmax_i8: bad arguments");
     TREC_REQUIRE(!wg_class || wg_scale, "trec_score_gemm_blockmax_i8: wg_class comes with wg_scale");
     TREC_REQUIRE(kpad == 64 || kpad == 128, "trec_score_gemm_blockmax_i8: kpad must be 64 or 128");
@@ -974,35 +721,6 @@ extern "C" int trec_score_gemm_blockmax_i8(const void* users_q, const void* item
     p.wg_scale = wg_scale; p.wg_class = item_bias_q ? wg_class : nullptr; p.bias_stride = n_items;
     hipStream_t st = (hipStream_t)stream;
     const bool bias = user_bias || item_bias_q;
-    // "blockmax_i8_mfma": 1 (default) = v_mfma_i32_16x16x64_i8, 0 = v_mfma_i32_32x32x32_i8 (A/B runs)
-    if (trec_get_tuning("blockmax_i8_mfma", 1) != 0) {
-#define TREC_I8X3(KTV, TKV, NUBV, NWV, BTV) (bias ? launch_i8x16<KTV, true, TKV, NUBV, NWV, BTV>(p, sb_rows, st) : launch_i8x16<KTV, false, TKV, NUBV, NWV, BTV>(p, sb_rows, st))
-#define TREC_I8X2(KTV, TKV, NUBV, NWV) (tile == 256 && sb_rows % 256 == 0 ? TREC_I8X3(KTV, TKV, NUBV, NWV, 256) : TREC_I8X3(KTV, TKV, NUBV, NWV, 128))
-#define TREC_I8X(KTV, TKV) (users == 192 ? (waves == 8 ? TREC_I8X2(KTV, TKV, 12, 8) : TREC_I8X2(KTV, TKV, 12, 4)) \
-                                       : (waves == 8 ? TREC_I8X2(KTV, TKV, 8, 8) : TREC_I8X2(KTV, TKV, 8, 4)))
-        const int tile = trec_get_tuning("blockmax_i8_tile", 128);             // item rows per tile: 128 or 256
-        const int waves = trec_get_tuning("blockmax_i8_waves", 4);             // waves per workgroup: 4 or 8
-        // users per wave: 192 (12 blocks of 16: a third fewer LDS reads and tile streams per flop; 78.8 vs 81.9 ms at 1M x 1M
-        // with the 10-slot lists, profiles/r02_power_trace_i8.txt) unless the 16-slot lists need the registers
-        const int users = trec_get_tuning("blockmax_i8_users", top_k > 10 ? 128 : 192);
-        // the late-prefetch form exists for the default shape only (K = 128, 10-slot lists, 192 users per wave, 4 waves, 128-row tiles)
-        // where a step's operand prefetch sits (see the kernel header): 1 (default, every shape) = after the step's MFMAs;
-        // 0 / 2 / 3 = the first form / mid-step / pinned interleave, for the default shape only (A/B: 78.1 / 77.2 / 75.5 ms against
-        // 75.7 for form 1 on one box, 1M x 1M)
-        const int rdl = trec_get_tuning("blockmax_i8_rdlate", 1);
-        if (kpad == 128 && top_k == 10 && users == 192 && waves == 4 && tile == 128 && rdl != 1) {
-            if (rdl == 2) return bias ? launch_i8x16<128, true, 10, 12, 4, 128, 2>(p, sb_rows, st) : launch_i8x16<128, false, 10, 12, 4, 128, 2>(p, sb_rows, st);
-            if (rdl == 3) return bias ? launch_i8x16<128, true, 10, 12, 4, 128, 3>(p, sb_rows, st) : launch_i8x16<128, false, 10, 12, 4, 128, 3>(p, sb_rows, st);
-            return bias ? launch_i8x16<128, true, 10, 12, 4, 128, 0>(p, sb_rows, st) : launch_i8x16<128, false, 10, 12, 4, 128, 0>(p, sb_rows, st);
-        }
-        if (kpad == 128) return top_k == 0 ? TREC_I8X(128, 0) : (top_k == 10 ? TREC_I8X(128, 10) : TREC_I8X(128, 16));
-        return top_k == 0 ? TREC_I8X(64, 0) : (top_k == 10 ? TREC_I8X(64, 10) : TREC_I8X(64, 16));
-#undef TREC_I8X
-#undef TREC_I8X2
-#undef TREC_I8X3
-    }
-#define TREC_I8(KTV, TKV) (bias ? launch_i8<KTV, true, 4, 2, TKV>(p, sb_rows, st) : launch_i8<KTV, false, 4, 2, TKV>(p, sb_rows, st))
-    if (kpad == 128) return top_k == 0 ? TREC_I8(128, 0) : (top_k == 10 ? TREC_I8(128, 10) : TREC_I8(128, 16));
-    return top_k == 0 ? TREC_I8(64, 0) : (top_k == 10 ? TREC_I8(64, 10) : TREC_I8(64, 16));
-#undef TREC_I8
+    if (kpad == 128) return bias ? launch_i8x16_lists<128, true>(p, sb_rows, st) : launch_i8x16_lists<128, false>(p, sb_rows, st);
+    return bias ? launch_i8x16_lists<64, true>(p, sb_rows, st) : launch_i8x16_lists<64, false>(p, sb_rows, st);
 }

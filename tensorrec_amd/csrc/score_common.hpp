@@ -1,5 +1,5 @@
 // tensorrec_amd/csrc/score_common.hpp -- launch parameters shared by the score kernels (score_gemm.hip,
-// score_blockmax.hip).
+// score_blockmax.hip, score_blockmax_i8.hip) and their callers in topk_cascade.hip.
 #pragma once
 #include "common.hpp"
 
@@ -58,7 +58,7 @@ struct ScoreParams {
     int top_k;
     int top_tag;                   // int8 BLOCKMAX: the lower bounds carry the superblock's index inside its chunk in their low
                                    // TREC_LB_TAG_BITS bits (lb_tag below): the pre-refinement of the cascade needs to know WHICH
-                                   // superblocks hold a user's k largest lower bounds (trec_topk_prerefine_rows)
+                                   // superblocks hold a user's k largest lower bounds (trec_topk_prerefine_rows_pos)
 };
 
 // A lower bound with an index in its low bits.  tagged <= lb always (a smaller lower bound is still a lower bound: at most two
@@ -95,7 +95,7 @@ __device__ __forceinline__ float i8_pair_err(float nx, float ex, float cu, float
 // software-pipelined BLOCKMAX kernel (score_blockmax.hip): bf16 dot / cosine, kpad 64 or 128.  Returns
 // TREC_ERR_UNSUPPORTED when the configuration is not covered (the caller then uses the generic kernel).
 int launch_blockmax_pipelined(const ScoreParams& p, int kt, hipStream_t stream);
-// the 16x16x32 bf16 form for the filters (any summation order): TREC_ERR_UNSUPPORTED when switched off / not covered
+// the 16x16x32 bf16 form for the filters (any summation order): TREC_ERR_UNSUPPORTED when the configuration is not covered
 int launch_blockmax_filter16(const ScoreParams& p, int kt, hipStream_t stream);
 // grouped bf16 form (stage 2 of the int8 cascade): see score_blockmax.hip
 int launch_blockmax_pipelined_grouped(const ScoreParams& p, int kt, hipStream_t stream);

@@ -450,7 +450,6 @@ extern "C" int trec_score_gemm_refine_candidates(const void* users_bf16, const v
     TREC_REQUIRE(kpad == 64 || kpad == 128, "trec_score_gemm_refine_candidates: kpad must be 64 or 128");
     TREC_REQUIRE(n_rows_g % GROUP_ROWS == 0 && n_rows_g < ((int64_t)1 << 40), "trec_score_gemm_refine_candidates: n_rows_g % 512 != 0");
     TREC_REQUIRE(sb_rows >= 64 && sb_rows % 64 == 0 && sb_rows <= 65536, "trec_score_gemm_refine_candidates: sb_rows must be a multiple of 64, <= 65536");
-    TREC_REQUIRE(trec_get_tuning("blockmax_bf16_mfma16", 1) != 0, "trec_score_gemm_refine_candidates: needs the 16x16x32 kernel (tuning blockmax_bf16_mfma16)");
     if (n_rows_g == 0) return TREC_OK;
     TREC_REQUIRE(n_rows_g / GROUP_ROWS < ((int64_t)1 << 31), "trec_score_gemm_refine_candidates: too many workgroups");
     ScoreParams p = {};
@@ -484,7 +483,6 @@ extern "C" int trec_score_gemm_refine_candidates_marked(const void* users_bf16, 
     TREC_REQUIRE(kpad == 64 || kpad == 128, "trec_score_gemm_refine_candidates_marked: kpad must be 64 or 128");
     TREC_REQUIRE(n_rows_g % GROUP_ROWS == 0 && n_rows_g < ((int64_t)1 << 40), "trec_score_gemm_refine_candidates_marked: n_rows_g % 512 != 0");
     TREC_REQUIRE(sb_rows >= 64 && sb_rows % 64 == 0 && sb_rows <= 65536, "trec_score_gemm_refine_candidates_marked: sb_rows must be a multiple of 64, <= 65536");
-    TREC_REQUIRE(trec_get_tuning("blockmax_bf16_mfma16", 1) != 0, "trec_score_gemm_refine_candidates_marked: needs the 16x16x32 kernel (tuning blockmax_bf16_mfma16)");
     if (n_rows_g == 0) return TREC_OK;
     TREC_REQUIRE(n_rows_g / GROUP_ROWS < ((int64_t)1 << 31), "trec_score_gemm_refine_candidates_marked: too many workgroups");
     ScoreParams p = {};

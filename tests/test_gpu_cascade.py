@@ -234,6 +234,11 @@ def test_int8_table_is_exact_integer_arithmetic_and_bound_holds(ops):
     N.call("trec_score_gemm_blockmax_i8", N.ptr(uop.i8), N.ptr(iop.i8), d, n_u, n_i, N.ptr(dub), N.ptr(iop.bias_q),
            N.ptr(iop.scales), N.ptr(iop.sb_stats), sb, n_chunks, N.ptr(table_t), n_u, N.ptr(uerr), N.ptr(ctop_t), 10 | 0x100, None, None, 0)
     assert np.array_equal(table_t.cpu().numpy(), got)
+    # the form without lists (user_err, chunk_top NULL, top_k = 0): the same table, bit for bit
+    table_0 = torch.full((n_sb, n_u), float("nan"), dtype=torch.float32, device="cuda")
+    N.call("trec_score_gemm_blockmax_i8", N.ptr(uop.i8), N.ptr(iop.i8), d, n_u, n_i, N.ptr(dub), N.ptr(iop.bias_q),
+           N.ptr(iop.scales), N.ptr(iop.sb_stats), sb, n_chunks, N.ptr(table_0), n_u, None, None, 0, None, None, 0)
+    assert np.array_equal(table_0.cpu().numpy().view(np.int32), got.view(np.int32))
     tg = ctop_t.cpu().numpy().reshape(n_ch, 10, n_u)
     bits = tg.view(np.int32).astype(np.int64)
     key = np.where(bits >= 0, bits, -(bits & 0x7FFFFFFF))                     # the monotone integer key of lb_tag (score_common.hpp)
