@@ -751,6 +751,29 @@ int trec_exclude_rank_adjust(const int64_t* pair_ptr, const int32_t* t_idx, cons
 int trec_topk_drop_self(const float* in_vals, const int32_t* in_idx, int32_t kf, int64_t n_rows, const int32_t* self_id,
                         float* out_vals, int32_t* out_idx, void* stream);
 
+/* ---- EXTENSION: candidate sets (csrc/candidate_sets.hip, docs/candidate_sets.md; no TF counterpart) -----------------------
+ * Each user's candidate items as one CSR in the exclusions' convention: ptr int64 [n_rows + 1] (absolute positions), idx int32
+ * sorted and de-duplicated per row, rows (nullable): row r of the call uses CSR row rows[r] (identity when NULL).
+ * trec_candset_scores: out[p] = exact score of (user operand row r, item idx[p]) for every position p of row r's segment -- the
+ * chain of trec_pair_score_exact bit for bit (operands fp32 [n, ld] from trec_score_prep, ld a multiple of 4, 16-byte aligned,
+ * 1 <= kdim <= 256; mode / biases / squared norms as there).  nnz = ptr[n_rows] - ptr[0] (identity rows) sizes the launch; an id
+ * outside [0, n_items) scores NaN.  Without `rows` consecutive users share 64-pair tiles; with it a tile holds one user's pairs.
+ * trec_candset_topk: scores [nnz] in CSR order -> out [n_rows, k] (1 <= k <= 1024): every segment's exact top-k by (value desc,
+ * id asc), -inf / -1 beyond its entries.  -0.0 ties +0.0; a NaN ranks behind -inf; a score with the bits 0xFFFFFFFF is absent.
+ * Segments of at most 256 entries take a wave each; long_rows int32 [n_long] must list EVERY row of the call with a longer
+ * segment (one workgroup each, the selection of trec_topk_rows_excluded).
+ * trec_candset_rank_count: targets grouped by user (pair_ptr int64 [n_users + 1], t_idx / t_score) against the users' candidate
+ * lists (ptr / idx / score, same user rows): counts[t] = #{x in C_u, x != t : s_x > s_t or (s_x == s_t and x < t)}, so
+ * count + 1 is the target's rank among its user's candidates whether or not the target is listed.                         */
+int trec_candset_scores(const float* users_f32, const float* items_f32, int64_t ld, int32_t kdim, const int64_t* ptr,
+                        const int32_t* idx, const int32_t* rows, int64_t n_rows, int64_t nnz, int64_t n_items,
+                        const float* user_bias, const float* item_bias, int32_t mode, const float* user_sqnorm,
+                        const float* item_sqnorm, float* out, void* stream);
+int trec_candset_topk(const float* scores, const int64_t* ptr, const int32_t* idx, const int32_t* rows, int64_t n_rows, int32_t k,
+                      const int32_t* long_rows, int64_t n_long, float* out_vals, int32_t* out_idx, void* stream);
+int trec_candset_rank_count(const int64_t* pair_ptr, const int32_t* t_idx, const float* t_score, const int64_t* ptr,
+                            const int32_t* idx, const float* score, int64_t n_users, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

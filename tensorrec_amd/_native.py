@@ -165,6 +165,9 @@ SIGNATURES = {
     "trec_topk_rows_excluded": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "trec_exclude_rank_adjust": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_topk_drop_self": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "trec_candset_scores": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "trec_candset_topk": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
+    "trec_candset_rank_count": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
 }
 
 _lib = None

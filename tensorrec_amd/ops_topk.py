@@ -1431,3 +1431,57 @@ def topk_rows_excluded(scores, k, ex_ptr=None, ex_idx=None, rows=None):
         N.call("trec_topk_rows_excluded", N.ptr(scores), scores.stride(0), n, n_i, int(k), N.ptr(ex_ptr), N.ptr(ex_idx), N.ptr(rows),
                N.ptr(vals), N.ptr(idx))
     return vals, idx
+
+
+CANDSET_SHORT_MAX = 256       # csrc/candidate_sets.hip: the longest segment one wave ranks; longer ones are listed by the host
+CANDSET_KDIM_MAX = 256
+
+
+def candset_scores(users_f32, items_f32, kpad, d, ptr, idx, nnz, user_bias=None, item_bias=None, mode=MODE_DOT, user_sq=None,
+                   item_sq=None, rows=None, out=None):
+    """Exact fp32 scores of every pair a candidate CSR lists, in CSR order (csrc/candidate_sets.hip, kernel A): the chain of
+    pair_scores_exact bit for bit, item rows gathered coalesced through LDS tiles.  ``users_f32`` / ``items_f32``: score_prep's fp32
+    operands [n, kpad]; ``ptr``: device int64 [n_rows + 1] absolute positions into ``idx`` (device int32, sorted per row); row r of
+    the operand scores CSR row r, or ``rows[r]`` (device int32).  ``nnz``: entries of ``idx`` -- the returned tensor has one score
+    per entry; positions outside the call's rows are left as they were (zero when allocated here)."""
+    n_rows = int(users_f32.shape[0]) if rows is None else int(rows.numel())
+    if int(ptr.numel()) < (n_rows + 1 if rows is None else 2):
+        raise ValueError("candset_scores: ptr is shorter than the call's rows")
+    if not 1 <= int(d) <= CANDSET_KDIM_MAX:
+        raise ValueError("candset_scores supports 1 <= d <= %d (got %r)" % (CANDSET_KDIM_MAX, d))
+    if out is None:
+        out = torch.zeros((int(idx.numel()),), dtype=torch.float32, device=users_f32.device)
+    with _timed("candset_scores"):
+        N.call("trec_candset_scores", N.ptr(users_f32), N.ptr(items_f32), int(kpad), int(d), N.ptr(ptr), N.ptr(idx), N.ptr(rows),
+               n_rows, int(nnz), int(items_f32.shape[0]), N.ptr(user_bias), N.ptr(item_bias), int(mode), N.ptr(user_sq),
+               N.ptr(item_sq), N.ptr(out))
+    return out
+
+
+def candset_topk(scores, ptr, idx, k, long_rows=None, rows=None, n_rows=None):
+    """Exact top-k of every segment of a candidate CSR (kernel B): (values [n_rows, k], ids int32 [n_rows, k]) by (value desc, id
+    asc), -inf / -1 beyond a segment's entries.  ``scores``: device fp32, one per entry of ``idx``; ``long_rows``: device int32 rows
+    of the call whose segment exceeds CANDSET_SHORT_MAX entries -- every one of them (candidate_sets.long_rows), None for none."""
+    if not 1 <= int(k) <= EXCLUDE_K_MAX:
+        raise ValueError("candset_topk supports 1 <= k <= %d (got %r)" % (EXCLUDE_K_MAX, k))
+    if n_rows is None:
+        n_rows = int(rows.numel()) if rows is not None else int(ptr.numel()) - 1
+    n_long = 0 if long_rows is None else int(long_rows.numel())
+    vals = torch.empty((n_rows, int(k)), dtype=torch.float32, device=ptr.device)
+    ids = torch.empty((n_rows, int(k)), dtype=torch.int32, device=ptr.device)
+    with _timed("candset_topk"):
+        N.call("trec_candset_topk", N.ptr(scores), N.ptr(ptr), N.ptr(idx), N.ptr(rows), n_rows, int(k),
+               N.ptr(long_rows) if n_long else None, n_long, N.ptr(vals), N.ptr(ids))
+    return vals, ids
+
+
+def candset_rank_count(pair_ptr, t_idx, t_score, ptr, idx, score):
+    """Kernel C: for each target t of user u (``pair_ptr`` device int64 [n_users + 1] into ``t_idx`` / ``t_score``), the number of
+    u's candidates other than t that stand ahead of it: #{x in C_u, x != t : s_x > s_t or (s_x == s_t and x < t)} -> int32 counts
+    (rank = count + 1).  ``ptr`` / ``idx`` / ``score``: the candidate CSR over the same user rows and its scores."""
+    n_users = int(pair_ptr.numel()) - 1
+    counts = torch.zeros((int(t_idx.numel()),), dtype=torch.int32, device=pair_ptr.device)
+    with _timed("candset_rank_count"):
+        N.call("trec_candset_rank_count", N.ptr(pair_ptr), N.ptr(t_idx), N.ptr(t_score), N.ptr(ptr), N.ptr(idx), N.ptr(score),
+               n_users, N.ptr(counts))
+    return counts

@@ -28,6 +28,7 @@ from scipy import sparse as sp
 from . import ops
 from . import exclusion as _excl
 from . import similar as _sim
+from . import candidate_sets as _cand
 from . import _native as N
 from .errors import (
     ModelNotBiasedException, ModelNotFitException, ModelWithoutAttentionException, BatchNonSparseInputException
@@ -1072,7 +1073,8 @@ class TensorRec(object):
         return _to_host(rank_predictions(pred))
 
     @_on_model_device
-    def predict_rank_of_interactions(self, user_features, item_features, interactions, user_batch_size=None, exclude=None):
+    def predict_rank_of_interactions(self, user_features, item_features, interactions, user_batch_size=None, exclude=None,
+                                     candidates=None):
         """EXTENSION: the ranks ``predict_rank`` would give, but only at the positive entries of ``interactions`` --
         all the evaluation metrics need (eval.py multiplies the [n_users, n_items] rank matrix by the positive mask).
         Users are walked in tiles: a [tile, n_items] score slab stays on the device and K4 ranks each positive pair
@@ -1084,7 +1086,12 @@ class TensorRec(object):
         items not excluded for its user, 1 + #{j not in E_u : s_j > s_t or (s_j == s_t and j < t)}, so every metric of eval.py on
         the result is the filtered metric.  A positive pair that is also excluded raises ValueError.  The count over all items
         is corrected by the excluded items ahead of the target (trec_exclude_rank_adjust), whose scores come from the chain the
-        count used: the fused path's exact pair chain, or the score slab."""
+        count used: the fused path's exact pair chain, or the score slab.
+
+        ``candidates`` (scipy sparse, the convention of predict_top_k's): sampled-negative evaluation -- a pair's rank counts only
+        the user's candidates, 1 + #{j in C_u, j != t : s_j > s_t or (s_j == s_t and j < t)}, whether or not t itself is stored
+        in C_u; with ``exclude`` the set is C_u \\ E_u.  Every metric of eval.py on the result is the sampled metric
+        (docs/candidate_sets.md)."""
         from .eval import PairRanks
         self._check_fit('predict_rank_of_interactions')
         uf, itf = self._inference(user_features, item_features)
@@ -1099,7 +1106,7 @@ class TensorRec(object):
         if not pos.all():
             rows, cols, vals = rows[pos], cols[pos], vals[pos]
         n_users, n_items = uf.shape[0], itf.shape[0]
-        if user_batch_size is None:
+        if user_batch_size is None and candidates is None:
             user_batch_size = max(64, min(n_users, (1 << 29) // max(1, n_items)))       # <= 2 GB of fp32 scores
         device = self._store.device
         ex = None
@@ -1112,6 +1119,12 @@ class TensorRec(object):
                                      "ranking" % n_both)
                 ex_rows = np.repeat(np.arange(n_users, dtype=np.int32), np.diff(ex_indptr))
                 ex = (ex_indptr, ex_indices, ex_rows)
+        if candidates is not None:
+            c_indptr, c_indices = _cand.candidate_csr(candidates, n_users, n_items)
+            if ex is not None:
+                c_indptr, c_indices = _cand.difference_csr(c_indptr, c_indices, ex[0], ex[1], n_items)
+            ranks = self._candidate_pair_ranks(uf, itf, rows, cols, c_indptr, c_indices, user_batch_size)
+            return PairRanks(rows, ranks, vals, n_users)
         ranks = np.zeros(len(rows), np.int32)
         bounds = np.searchsorted(rows, np.arange(0, n_users + user_batch_size, user_batch_size))
         # one taste, built-in prediction graph, fp32: no slab at all -- the count is the epilogue of the fp32 MFMA score
@@ -1193,7 +1206,7 @@ class TensorRec(object):
 
     @_on_model_device
     def predict_top_k(self, user_features, item_features, k=10, user_batch_size=None, return_device=False,
-                      item_sharded=False, item_offset=0, return_route=False, exclude=None):
+                      item_sharded=False, item_offset=0, return_route=False, exclude=None, candidates=None):
         """EXTENSION: the k best items per user -- (scores [n_users, k] float32, item ids [n_users, k] int32),
         ordered like the first k ranks of ``predict_rank`` -- computed by the fused MFMA score + top-k kernel without
         materialising [n_users, n_items] (which is 4 TB at 1M x 1M).  ``user_batch_size`` None (default): as many users per
@@ -1223,13 +1236,30 @@ class TensorRec(object):
         slabs; the slab route masks its slabs directly (docs/exclusion.md).  ``last_route`` then holds "exclude": {"k_fetch",
         "n_excluded", "n_fallback"}.  None, or a matrix without a non-zero entry: exactly the call without it.  Not with
         ``item_sharded`` / ``item_offset`` (a follow-up: filter after the replicated merge, tier 2 per shard) and not beyond
-        k = 1,024 (ValueError)."""
+        k = 1,024 (ValueError).
+
+        ``candidates`` (scipy sparse, at most [n_users, n_items], the same convention: every stored entry != 0 makes that item
+        a candidate of that user; a missing or empty row is an empty set): the first k places of ``predict_rank``'s order among
+        the user's candidates only, padded with (-inf, -1) beyond them -- on fp32 models bit-identical to ``predict()[u, C_u]``
+        ordered that way, on bf16 models on the bf16 scores.  With ``exclude`` the set is C_u \\ E_u.  One taste, no attention,
+        fp32 and n_components <= 256: only the listed pairs are scored ("form": "pairs", nothing of size users x items is made);
+        otherwise score slabs of the code ``predict`` uses are read at the listed cells ("form": "slab").  ``last_route`` is then
+        {"route": "candidate_sets", "form", "k", "n_candidates", "user_batch_size", "n_items", "sharded": False}.  Not with item
+        shards, not beyond k = 1,024 (ValueError).  docs/candidate_sets.md."""
         self._check_fit('predict_top_k')
         if int(k) < 1:
             raise ValueError("predict_top_k needs k >= 1 (got %r)" % (k,))
         if not self._is_engine_graph():
             raise ValueError("predict_top_k needs a built-in prediction graph")
+        if candidates is not None:
+            _cand.check_call(k, item_sharded, item_offset, ops.EXCLUDE_K_MAX)
         uf, itf = self._inference(user_features, item_features)
+        if candidates is not None:
+            c_indptr, c_indices = _cand.candidate_csr(candidates, uf.shape[0], itf.shape[0])
+            if exclude is not None:
+                e_indptr, e_indices = _excl.exclusion_csr(exclude, uf.shape[0], itf.shape[0])
+                c_indptr, c_indices = _cand.difference_csr(c_indptr, c_indices, e_indptr, e_indices, itf.shape[0])
+            return self._candidate_top_k(uf, itf, c_indptr, c_indices, int(k), user_batch_size, return_device, return_route)
         ex = None
         if exclude is not None:
             ex_indptr, ex_indices = _excl.exclusion_csr(exclude, uf.shape[0], itf.shape[0])
@@ -1427,6 +1457,130 @@ class TensorRec(object):
         if return_device:
             return _ret(vals, idx)
         return _ret(_to_host(vals), _to_host(idx))
+
+    # ------------------------------------------------------------------------------------------ candidate sets
+    def _candidate_form(self):
+        """"pairs": only the listed pairs are scored, by the exact chain on score_prep's fp32 operands; "slab": everything else."""
+        if self._is_engine_graph() and not self._multi() and self.precision == 'fp32' and self.n_components <= _cand.PAIRS_D_MAX:
+            return "pairs"
+        return "slab"
+
+    def _candidate_slab_step(self, n_items, n_tastes, attention, user_batch_size):
+        planes = 1 + (2 * n_tastes if attention else (n_tastes if n_tastes > 1 else 0))
+        step = max(1, (1 << 28) // max(1, n_items * planes))
+        return step if user_batch_size is None else max(1, min(step, int(user_batch_size)))
+
+    def _candidate_scores(self, form, user_reprs, attn_reprs, item_repr, user_bias, item_bias, indptr, indices, user_batch_size,
+                          extra=None):
+        """Generator over the user batches of a candidate-set call: (s, e, ptr_d, idx_d, scores, extra scores).  ``ptr_d``: device
+        int64 [e - s + 1] counted from the batch's first entry, ``idx_d`` / ``scores``: the batch's candidate ids and their scores in
+        CSR order.  ``extra`` = (rows, cols) host int32 arrays sorted by row: further pairs scored by the same code, yielded per
+        batch as (p0, p1, device scores) -- the targets of the pair ranks."""
+        device = self._store.device
+        graph = self.prediction_graph_factory
+        n_items = int(item_repr.shape[0])
+        ub = user_bias if self.biased else None
+        ib = item_bias if self.biased else None
+        if form == "pairs":
+            want_sq = graph.engine_mode == ops.MODE_EUCLIDEAN
+            d = int(user_reprs[0].shape[1])
+            u_op, u_sq, kpad = ops.score_prep(user_reprs[0], ops.DTYPE_F32, normalize=graph.engine_normalize, want_sqnorm=want_sq)
+            i_op, i_sq, _ = ops.score_prep(item_repr, ops.DTYPE_F32, normalize=graph.engine_normalize, want_sqnorm=want_sq)
+            ubc = ub.detach().reshape(-1).contiguous() if ub is not None else None
+            ibc = ib.detach().reshape(-1).contiguous() if ib is not None else None
+            batches = _cand.cut_batches(indptr, user_batch_size)
+        else:
+            step = int(user_batch_size)
+            batches = [(s, min(s + step, len(indptr) - 1)) for s in range(0, len(indptr) - 1, step)]
+        if extra is not None:
+            x_rows, x_cols = extra
+            x_bounds = np.searchsorted(x_rows, np.asarray([b[0] for b in batches] + [len(indptr) - 1]))
+        for b, (s, e) in enumerate(batches):
+            q0, q1 = int(indptr[s]), int(indptr[e])
+            ptr_d = torch.from_numpy(indptr[s:e + 1] - q0).to(device)
+            idx_d = torch.from_numpy(np.ascontiguousarray(indices[q0:q1])).to(device)
+            xs = None
+            if extra is not None:
+                p0, p1 = int(x_bounds[b]), int(x_bounds[b + 1])
+                xu_d = torch.from_numpy(np.ascontiguousarray(x_rows[p0:p1] - s)).to(device)
+                xi_d = torch.from_numpy(np.ascontiguousarray(x_cols[p0:p1])).to(device)
+            if form == "pairs":
+                sq = u_sq[s:e] if u_sq is not None else None
+                ubs_ = ubc[s:e] if ubc is not None else None
+                scores = ops.candset_scores(u_op[s:e], i_op, kpad, d, ptr_d, idx_d, q1 - q0, ubs_, ibc, graph.engine_mode, sq, i_sq)
+                if extra is not None:
+                    xs = (p0, p1, xi_d, ops.pair_scores_exact(u_op[s:e], i_op, kpad, d, xu_d, xi_d, ubs_, ibc, graph.engine_mode,
+                                                             sq, i_sq))
+            else:
+                qb = ub[s:e] if ub is not None else None
+                attn = [a[s:e] for a in attn_reprs] if attn_reprs is not None else None
+                if self._is_engine_graph():
+                    slab = self._score_slab([u[s:e] for u in user_reprs], attn, item_repr, qb, ib)
+                elif self._multi():
+                    slab = self._dense_multi([u[s:e] for u in user_reprs], attn, item_repr, qb, ib)
+                else:
+                    slab = self._dense_prediction(user_reprs[0][s:e], item_repr, qb, ib)
+                cu = torch.repeat_interleave(torch.arange(e - s, device=device), (ptr_d[1:] - ptr_d[:-1]))
+                scores = slab[cu, idx_d.long()].to(torch.float32).contiguous()
+                if extra is not None:
+                    xs = (p0, p1, xi_d, slab[xu_d.long(), xi_d.long()].to(torch.float32).contiguous())
+            yield s, e, ptr_d, idx_d, scores, xs
+
+    def _candidate_top_k(self, uf, itf, indptr, indices, k, user_batch_size, return_device, return_route):
+        """predict_top_k(candidates=...): kernel A (pairs form) or the score slabs (slab form) give the candidates' scores in CSR
+        order, kernel B selects each segment's exact top-k."""
+        form = self._candidate_form()
+        n_users, n_items = uf.shape[0], itf.shape[0]
+        device = self._store.device
+        with torch.no_grad(), variable_scope(self._store):
+            user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
+            if form == "pairs":
+                ubs = _cand.default_user_batch(indptr) if user_batch_size is None else max(1, int(user_batch_size))
+            else:
+                ubs = self._candidate_slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
+            self.last_route = {"route": "candidate_sets", "form": form, "k": int(k), "n_candidates": int(len(indices)),
+                               "user_batch_size": int(ubs), "n_items": int(n_items), "sharded": False}
+            vals, idx = [], []
+            for s, e, ptr_d, idx_d, scores, _ in self._candidate_scores(form, user_reprs, attn_reprs, item_repr, user_bias,
+                                                                         item_bias, indptr, indices, ubs):
+                lr = _cand.long_rows(indptr, s, e)
+                v, i = ops.candset_topk(scores, ptr_d, idx_d, k, long_rows=torch.from_numpy(lr).to(device) if len(lr) else None)
+                vals.append(v)
+                idx.append(i)
+            if vals:
+                vals, idx = torch.cat(vals), torch.cat(idx)
+            else:
+                vals = torch.empty((0, k), dtype=torch.float32, device=device)
+                idx = torch.empty((0, k), dtype=torch.int32, device=device)
+        if not return_device:
+            vals, idx = _to_host(vals), _to_host(idx)
+        return (vals, idx, dict(self.last_route)) if return_route else (vals, idx)
+
+    def _candidate_pair_ranks(self, uf, itf, rows, cols, indptr, indices, user_batch_size):
+        """predict_rank_of_interactions(candidates=...): int32 ranks of the pairs (rows, cols), sorted by row, among each user's
+        candidates: targets and candidates scored by the same code, kernel C counts."""
+        form = self._candidate_form()
+        n_users, n_items = uf.shape[0], itf.shape[0]
+        device = self._store.device
+        ranks = np.zeros(len(rows), np.int32)
+        if len(rows) == 0:
+            return ranks
+        with torch.no_grad(), variable_scope(self._store):
+            user_reprs, attn_reprs, item_repr, user_bias, item_bias, _ = self._representations(uf, itf)
+            if form == "pairs":
+                ubs = _cand.default_user_batch(indptr) if user_batch_size is None else max(1, int(user_batch_size))
+            else:
+                ubs = self._candidate_slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
+            rows32 = np.ascontiguousarray(rows, dtype=np.int32)
+            for s, e, ptr_d, idx_d, scores, xs in self._candidate_scores(form, user_reprs, attn_reprs, item_repr, user_bias,
+                                                                          item_bias, indptr, indices, ubs, extra=(rows32, cols)):
+                p0, p1, xi_d, tgt = xs
+                if p0 == p1:
+                    continue
+                pair_ptr = (np.searchsorted(rows32[p0:p1], np.arange(s, e + 1))).astype(np.int64)
+                counts = ops.candset_rank_count(torch.from_numpy(pair_ptr).to(device), xi_d, tgt, ptr_d, idx_d, scores)
+                ranks[p0:p1] = (counts + 1).cpu().numpy()
+        return ranks
 
     def _score_slab(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias):
         """[n_queries, n_items] scores of the slab passes of the top-k core, with the biases it is GIVEN (None: none): one taste is
