@@ -39,6 +39,7 @@ int trec_device_cu_count(void);
 /* benchmark-only switches between kernel variants (e.g. "spmm_rows", "spmm_nt"); never needed for correctness */
 int trec_set_tuning(const char* name, int32_t value);
 int trec_get_tuning(const char* name, int dflt);
+int trec_clear_tuning(const char* name);   /* back to "not set": trec_get_tuning returns its caller's default again */
 
 /* ---- K1: sparse features x dense weights ------------------------------------------------------------------
  * tf.sparse_tensor_dense_matmul: representation_graphs.py:40 (Linear), :119 (ReLU layer 1),

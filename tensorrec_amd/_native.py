@@ -29,6 +29,7 @@ SIGNATURES = {
     "trec_device_cu_count": [],
     "trec_set_tuning": [ctypes.c_char_p, _i32],
     "trec_get_tuning": [ctypes.c_char_p, ctypes.c_int],
+    "trec_clear_tuning": [ctypes.c_char_p],
     "trec_spmm_csr": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
     "trec_spmm_one_per_row": [_vp, _vp, _i64, _vp, _i32, _vp, _vp],
     "trec_spmm_csr_filter": [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -239,6 +240,11 @@ def call(name, *args):
 
 def set_tuning(name, value):
     load().trec_set_tuning(name.encode(), int(value))
+
+
+def clear_tuning(name):
+    """Back to "not set": the kernels use their own default again (which may depend on the call, e.g. pair_fwd_pp)."""
+    load().trec_clear_tuning(name.encode())
 
 
 def query(name, *args):

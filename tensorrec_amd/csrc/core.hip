@@ -35,6 +35,14 @@ extern "C" int trec_set_tuning(const char* name, int32_t value)
     return TREC_OK;
 }
 
+// back to "not set": a knob whose default depends on the call (pair_fwd_pp) has no value that restores it
+extern "C" int trec_clear_tuning(const char* name)
+{
+    if (!name) return TREC_ERR_INVALID;
+    tuning_map().erase(name);
+    return TREC_OK;
+}
+
 extern "C" int trec_get_tuning(const char* name, int dflt)
 {
     auto it = tuning_map().find(name ? name : "");

@@ -384,6 +384,7 @@ class _PairScore(torch.autograd.Function):
         N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(xu32), N.ptr(xi32), n_pairs, pairs_per_user, u.shape[1],
                mode, N.ptr(ub), N.ptr(ib), N.ptr(out), N.ptr(sqdist))
         ctx.sqdist = sqdist
+        ctx.stable_grouping = _LOCAL.deterministic_grouping      # (read here: the engine runs backward() on a thread of its own)
         ctx.save_for_backward(u, v)
         ctx.meta = (xu32, xi32, pairs_per_user, mode, ub is not None, ib is not None, inter)
         return out
@@ -429,7 +430,7 @@ class _PairScore(torch.autograd.Function):
             indptr_t, users_t, perm_t = inter.transposed()
             long_i = inter.max_col_nnz > SPLIT_T
         else:
-            indptr_t, users_t, perm_t = group_pairs_by_item(xu32, xi32, ppu, n_items)
+            indptr_t, users_t, perm_t = group_pairs_by_item(xu32, xi32, ppu, n_items, stable=ctx.stable_grouping)
             long_i = _sampled_buckets_long(n_pairs, n_items)
         if euclid or ((long_i or prefer) and can_split):
             dv = spmm_split(indptr_t, users_t, vals, perm_t, n_items, n_pairs, u, own=v if euclid else None)
@@ -452,7 +453,9 @@ _LOCAL = _Local()       # per THREAD: two models fitting in different threads mu
 
 class deterministic_grouping(object):
     """``with ops.deterministic_grouping(flag):`` -- group_pairs_by_item uses the stable (bit-reproducible) grouping inside the
-    block, in this thread only; the previous mode returns on exit (TensorRec(deterministic=True) wraps its fit calls in it)."""
+    block, in this thread only; the previous mode returns on exit (TensorRec(deterministic=True) wraps its fit calls in it).
+    The autograd functions whose backward groups pairs (pair_score, collapse_tastes) read the mode in their FORWARD pass and
+    hand it to their backward pass: the autograd engine runs backward() on its own thread, where this thread's mode is not seen."""
 
     def __init__(self, flag=True):
         self.flag = bool(flag)
@@ -493,17 +496,18 @@ def _loss_all_reduce(t):
     return t
 
 
-def group_pairs_by_item(xu32, xi32, pairs_per_user, n_items, workspace_with_counts=None, ranks=None, values=None):
+def group_pairs_by_item(xu32, xi32, pairs_per_user, n_items, workspace_with_counts=None, ranks=None, values=None, stable=None):
     """(indptr_t int64 [n_items+1], users_t int32 [n_pairs], perm_t int32 [n_pairs]) for a pair list, built on the
     device; the order of pairs inside an item's bucket is not fixed (atomic slot assignment).
     ``workspace_with_counts``: an int32 [2 * n_items] workspace whose first half already holds the histogram of the
     items (counted by the kernel that consumed the pairs) -- the histogram pass is then skipped; ``ranks`` (with it): the
     values those histogram atomics returned, which makes the fill pass atomic-free; ``values`` (with ranks): per-pair
     values to carry along -- the result is then (indptr_t, entries int32 [n_pairs, 2] = {user, value bits}, None): one
-    8-byte scattered store per pair, consumed by trec_spmm_csr_packed."""
+    8-byte scattered store per pair, consumed by trec_spmm_csr_packed.  ``stable``: the stable grouping or not; None: this
+    thread's ops.deterministic_grouping mode."""
     dev = xi32.device
     n_pairs = xi32.numel()
-    if _LOCAL.deterministic_grouping and n_pairs:
+    if (_LOCAL.deterministic_grouping if stable is None else stable) and n_pairs:
         # bit-reproducible fits (TensorRec(deterministic=True)): a STABLE sort by item keeps the pairs of a bucket in pair
         # order, so the fp32 sums over a bucket are added in the same order every run (the counting sort below orders a
         # bucket by atomic arrival).  Negative keys sort to the front and fall before indptr[0].
@@ -589,7 +593,7 @@ def pair_score(user_repr, item_repr, x_user, x_item, mode=MODE_DOT, user_bias=No
 
 
 # ------------------------------------------------------------------------------------------------ K9
-def _pair_bias_grads(g, xu32, xi32, ppu, inter, n_users, n_items, want_ub, want_ib):
+def _pair_bias_grads(g, xu32, xi32, ppu, inter, n_users, n_items, want_ub, want_ib, stable=None):
     """d user_bias / d item_bias of out[p] = ... + ub[user(p)] + ib[item(p)]: g summed per user / per item with the
     segmented K1 matvec over the pair structure (interactions: CSR + its transpose; samples: ppu consecutive pairs per
     user + a device counting sort by item).  Unstructured pair lists fall back to index_add_."""
@@ -609,7 +613,7 @@ def _pair_bias_grads(g, xu32, xi32, ppu, inter, n_users, n_items, want_ub, want_
         dub = spmv_raw(indptr_u, xi32, g, None, n_users, n_pairs, None, long_u)
     if want_ib:
         indptr_t, users_t, perm_t = inter.transposed() if inter is not None else \
-            group_pairs_by_item(xu32, xi32, ppu, n_items)
+            group_pairs_by_item(xu32, xi32, ppu, n_items, stable=stable)
         long_i = inter.max_col_nnz > SPLIT_T if inter is not None else _sampled_buckets_long(n_pairs, n_items)
         dib = spmv_raw(indptr_t, users_t, g, perm_t, n_items, n_pairs, None, long_i)
     return dub, dib
@@ -631,6 +635,7 @@ class _CollapseTastes(torch.autograd.Function):
         ctx.save_for_backward(preds, attn)
         ctx.meta = meta
         ctx.bias_shapes = (None if ub is None else ub.numel(), None if ib is None else ib.numel())
+        ctx.stable_grouping = _LOCAL.deterministic_grouping      # (as _PairScore: backward() runs on the engine's thread)
         return out
 
     @staticmethod
@@ -650,7 +655,7 @@ class _CollapseTastes(torch.autograd.Function):
             n_users = inter.shape[0] if inter is not None else (n // ppu if ppu > 0 else (n_ub or 0))
             n_items = inter.shape[1] if inter is not None else (n_ib or 0)
             dub, dib = _pair_bias_grads(g.reshape(-1), xu32, xi32, ppu, inter, n_users, n_items, n_ub is not None,
-                                        n_ib is not None)
+                                        n_ib is not None, stable=ctx.stable_grouping)
         elif bias_mode == 2:
             g2 = g.reshape(-1, span)
             if n_ub is not None:
