@@ -26,6 +26,7 @@
 // C. trec_candset_rank_count.  counts[t] = #{x in C_u, x != t : s_x > s_t or (s_x == s_t and x < t)} for targets grouped by user:
 //    trec_exclude_rank_adjust's comparison (listed_ahead), set instead of subtracted.
 #include "csr_select.hpp"
+#include "exact_finish.hpp"
 
 namespace {
 
@@ -114,15 +115,7 @@ template <bool U_LDS>
 __device__ __forceinline__ float cand_chain(float acc, const float* __restrict__ tile_row, const float* __restrict__ urow, int c0, int kdim)
 {
     const int cend = (kdim - c0) < CS_KC ? (kdim - c0) : CS_KC;        // columns of this block that belong to the chain
-    int c = 0;
-    for (; c + 4 <= cend; c += 4) {
-        const f32x4 b4 = *(const f32x4*)(tile_row + c);
-        const f32x4 a4 = *(const f32x4*)(urow + c0 + c);
-        acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-        acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-    }
-    for (; c < cend; ++c) acc = __fmaf_rn(urow[c0 + c], tile_row[c], acc);
-    return acc;
+    return exact_chain(acc, urow + c0, tile_row, cend, true);
 }
 
 __device__ __forceinline__ void wave_lds_sync()

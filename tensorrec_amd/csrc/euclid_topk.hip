@@ -69,12 +69,10 @@ __global__ __launch_bounds__(256) void euclid_certify_kernel(const int32_t* __re
 #pragma unroll
     for (int j = 0; j < EC_MAX; ++j) {
         if (j < k) {
-            const unsigned int hi = (unsigned int)(key[j] >> 32);
-            const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
             const bool empty = key[j] == 0ull;
-            const float v = empty ? -INFINITY : __uint_as_float(bits);
+            const float v = empty ? -INFINITY : merge_key_value(key[j]);
             ov[u * k + j] = v;
-            oi[u * k + j] = empty ? -1 : (int32_t)(~(unsigned int)key[j]);
+            oi[u * k + j] = empty ? -1 : merge_key_id(key[j]);
             if (j == k - 1) tk = v;
         }
     }

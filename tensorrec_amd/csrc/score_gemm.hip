@@ -549,12 +549,11 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     const int64_t u = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (u >= n_users) return;
     const int lane = lane_id();
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
     unsigned long long key[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
         const int j = c * 64 + lane;
-        key[c] = EMPTY;
+        key[c] = MERGE_KEY_EMPTY;
         if (j < n_cand) {
             const int32_t raw = pi[u * n_cand + j];
             if (raw >= 0) key[c] = merge_key(pv[u * n_cand + j], raw);
@@ -568,13 +567,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
         // every lane now holds the winner; retire it where it lives (indices are unique among real candidates)
 #pragma unroll
         for (int c = 0; c < CPL; ++c)
-            if (key[c] == best && best != EMPTY) key[c] = EMPTY;
-        if (lane == 0) {
-            const unsigned int hi = (unsigned int)(best >> 32);
-            const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-            ov[u * k + t] = (best == EMPTY) ? -INFINITY : __uint_as_float(bits);
-            oi[u * k + t] = (best == EMPTY) ? -1 : (int32_t)(~(unsigned int)best);
-        }
+            if (key[c] == best && best != MERGE_KEY_EMPTY) key[c] = MERGE_KEY_EMPTY;
+        if (lane == 0) store_place(ov, oi, u * k + t, best);
     }
 }
 

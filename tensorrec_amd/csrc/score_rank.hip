@@ -15,7 +15,7 @@
 // occupy several rows through row_user), the lane's 16 accumulator registers = 16 items of that row; the two half-waves
 // hold different items of the same row and add their counts at the end.  A target costs 16 compares + 16 adds per
 // 32-item block against 64 fp32 MFMAs (4096 cycles) -- up to ~30 targets per row ride under the MFMA time.
-#include "topk_common.hpp"
+#include "exact_finish.hpp"
 
 #define RANKC_QMAX 32
 
@@ -226,19 +226,7 @@ __global__ __launch_bounds__(256) void pair_score_exact_kernel(const float* __re
     const int64_t pidx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (pidx >= n_pairs) return;
     const int64_t u = xu[pidx], i = (int64_t)xi[pidx] - item_index_base;
-    const float* a = U + u * ld;
-    const float* b = V + i * ld;
-    float acc = 0.0f;
-    int k = 0;
-    if ((ld & 3) == 0) {
-        for (; k + 4 <= kdim; k += 4) {
-            const f32x4 a4 = *(const f32x4*)(a + k);
-            const f32x4 b4 = *(const f32x4*)(b + k);
-            acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-            acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-        }
-    }
-    for (; k < kdim; ++k) acc = __fmaf_rn(a[k], b[k], acc);
+    float acc = exact_chain(0.0f, U + u * ld, V + i * ld, kdim, (ld & 3) == 0);
     if (euclid) {
         float dist = (u_sq[u] - 2.0f * acc) + t_sq[i];
         dist = fmaxf(dist, 1e-16f);

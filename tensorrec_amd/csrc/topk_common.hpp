@@ -1,6 +1,7 @@
-// tensorrec_amd/csrc/topk_common.hpp -- helpers shared by the top-k kernels (score_gemm.hip, topk_filter.hip):
-// the (value desc, index asc) order of tf.nn.top_k (recommendation_graphs.py:80) as ONE unsigned 64-bit key, and its
-// wave-wide maximum by DPP.
+// tensorrec_amd/csrc/topk_common.hpp -- helpers shared by the top-k kernels: the (value desc, index asc) order of tf.nn.top_k
+// (recommendation_graphs.py:80) as ONE unsigned 64-bit key, its inverse, and its wave-wide maximum by DPP.  Included by
+// score_gemm.hip, score_rank.hip, topk_cascade.hip, euclid_topk.hip, by topk_filter.hip through exact_finish.hpp and by exclude.hip /
+// candidate_sets.hip through csr_select.hpp.
 #pragma once
 #include "common.hpp"
 #include <math.h>
@@ -20,6 +21,25 @@ __device__ __forceinline__ unsigned long long merge_key(float v, int32_t id)
     const unsigned int u = (v == 0.f) ? 0u : __float_as_uint(v);            // -0.0 and +0.0 compare equal: one key
     const unsigned int hi = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)hi << 32) | (unsigned int)(~id);
+}
+
+// merge_key(-inf, 0x7fffffff): below the key of every real entry -- an empty place
+constexpr unsigned long long MERGE_KEY_EMPTY = 0x007fffff80000000ull;
+
+__device__ __forceinline__ float merge_key_value(unsigned long long key)
+{
+    const unsigned int hi = (unsigned int)(key >> 32);
+    return __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
+}
+
+__device__ __forceinline__ int32_t merge_key_id(unsigned long long key) { return (int32_t)(~(unsigned int)key); }
+
+// place `at` of a result list: the key's value and id, -inf / -1 for an empty place
+__device__ __forceinline__ void store_place(float* __restrict__ ov, int32_t* __restrict__ oi, int64_t at, unsigned long long key)
+{
+    const bool empty = key == MERGE_KEY_EMPTY;
+    ov[at] = empty ? -INFINITY : merge_key_value(key);
+    oi[at] = empty ? -1 : merge_key_id(key);
 }
 
 template <int CTRL, int ROW_MASK>

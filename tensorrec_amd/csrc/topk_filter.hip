@@ -36,10 +36,8 @@
 // times round-to-nearest, covering truncating adders.  Every norm is computed in fp32 (relative error < K 2^-23) and
 // the sum is inflated by 2^-9; 1e-30 absorbs flushed denormals.  tests/test_gpu_filter.py measures max |sh - s| / eps
 // on random, adversarially aligned and near-tied inputs.
-#include "topk_common.hpp"
+#include "exact_finish.hpp"
 #include "score_common.hpp"
-
-#define FILTER_CMAX 64          // survivors per user the finish kernel can re-score (one per lane)
 
 __device__ __forceinline__ void atomic_max_nonneg(float* addr, float v)
 {
@@ -162,14 +160,9 @@ __global__ __launch_bounds__(256) void filter_floor_kernel(const float* __restri
     const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (u >= n_users) return;
     const float eps = filter_eps(ustats[u], user_bias ? fabsf(user_bias[u]) : 0.f, gstats, kdim);
-    const float t = tau[u];
-    float f = t - mult * eps;
-    bool bad = !(eps < INFINITY);                                               // inf or NaN
-    if (t == -INFINITY) f = -INFINITY;                                          // fewer than k superblocks: keep all
-    else if (!(f == f)) bad = true;
-    else f = float_pred(float_pred(f));
-    if (bad) f = -INFINITY;
-    floor_[u] = f;
+    const FloorBelow fb = floor_below(tau[u], mult * eps);                      // (tau = -inf: fewer than k superblocks, keep all)
+    const bool bad = !(eps < INFINITY) || fb.nan;                               // inf or NaN
+    floor_[u] = bad ? -INFINITY : fb.floor;
     if (flag) {
         flag[u] = bad ? 1 : 0;
         if (bad) atomicAdd(n_flagged, 1);
@@ -196,13 +189,9 @@ __global__ __launch_bounds__(256) void cascade_floor_kernel(float* __restrict__ 
         return;
     }
     const float eps = filter_eps(ustats[u], user_bias ? fabsf(user_bias[u]) : 0.f, gstats, kdim);
-    const float t = tau[u];
-    float f = t - eps;
-    bool bad = !(eps < INFINITY);                                               // inf or NaN
-    if (t == -INFINITY) f = -INFINITY;                                          // fewer than k superblocks: list everything
-    else if (!(f == f)) bad = true;
-    else f = float_pred(float_pred(f));
-    floor0[u] = bad ? INFINITY : f;                                             // a user without a usable bound lists nothing
+    const FloorBelow fb = floor_below(tau[u], eps);                             // (tau = -inf: fewer than k superblocks, list everything)
+    const bool bad = !(eps < INFINITY) || fb.nan;                               // inf or NaN
+    floor0[u] = bad ? INFINITY : fb.floor;                                      // a user without a usable bound lists nothing
     flag[u] = bad ? 1 : 0;
     if (bad) atomicAdd(n_flagged, 1);
 }
@@ -313,25 +302,22 @@ __global__ __launch_bounds__(256) void prerefine_tau_listed_kernel(const int32_t
     }
     if (!live || !ok[u]) return;
     const float eps = filter_eps(ustats[u], user_bias ? fabsf(user_bias[u]) : 0.f, gstats, kdim);
-    float t = m - eps;
-    if (eps < INFINITY && t == t && m < INFINITY) {
-        t = float_pred(float_pred(t));
+    const FloorBelow fb = floor_below(m, eps);
+    if (eps < INFINITY && !fb.nan && m < INFINITY) {                           // (an unusable bound leaves tau as it is)
+        const float t = fb.floor;
         if (t > tau[u]) {
             tau[u] = t;
             if (cand_floor && cand_floor[u] < INFINITY) {
-                const float f = float_pred(float_pred(t - eps));               // the provisional floor of the launches to come
+                const float f = floor_below(t, eps).floor;                     // the provisional floor of the launches to come
                 if (f > cand_floor[u]) cand_floor[u] = f;
             }
         }
     }
 }
 
-#ifndef FILTER_RB
-#define FILTER_RB 8          // survivors re-scored per round (their fp32 rows staged in LDS)
-#endif
 // The second half of the finish kernels: ``total`` (<= FILTER_CMAX) survivors' item ids sit in cand[] (LDS of this wave), the
-// user's row in registers uw.  Exact fp32 scores by the reference's k-ordered fmaf chain, then (s + b_u) + b_i, then the k
-// best by (value desc, index asc) to ov / oi.
+// user's row in registers uw.  Exact fp32 scores FILTER_RB survivors at a time (finish_stage_round), then the k best by (value
+// desc, index asc) to ov / oi.
 __device__ __forceinline__ void finish_rescore_topk(int total, const int32_t* cand, float* urow, float* rows, const f32x4 (&uw)[4],
                                                     int lane, int kdim, int chunks, int rstride, bool vec,
                                                     const float* __restrict__ V, int64_t ld_v, int32_t item_index_base,
@@ -339,68 +325,19 @@ __device__ __forceinline__ void finish_rescore_topk(int total, const int32_t* ca
                                                     float* __restrict__ ov, int32_t* __restrict__ oi, int64_t u)
 {
     __builtin_amdgcn_wave_barrier();              // cand[] / rows[] are private to this wave; a wave's DS operations execute in order
-    // ---- exact fp32 scores of the survivors: the reference's k-ordered fmaf chain, then (s + b_u) + b_i
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
-    unsigned long long key = EMPTY;                // lane r ends up holding survivor (round * FILTER_RB + r)'s key ...
-    unsigned long long mine = EMPTY;               // ... moved to lane (round * FILTER_RB + r) here
+    unsigned long long mine = MERGE_KEY_EMPTY;     // lane j: survivor j's key
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int ch = q * 64 + lane;
         if (ch < chunks) *(f32x4*)(urow + ch * 4) = uw[q];        // broadcast from LDS by every chain step
     }
-    const float* a = urow;
-    for (int r0 = 0; r0 < total; r0 += FILTER_RB) {
-        const int nr = (total - r0 < FILTER_RB) ? total - r0 : FILTER_RB;
-        for (int idx = lane; idx < nr * chunks; idx += 64) {
-            const int r = idx / chunks, ch = idx - r * chunks;
-            const float* src = V + (int64_t)(cand[r0 + r] - item_index_base) * ld_v + ch * 4;
-            f32x4 w;
-            if (vec) w = *(const f32x4*)src;
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-            }
-            *(f32x4*)(rows + r * rstride + ch * 4) = w;
-        }
-        const int32_t item = (lane < nr) ? cand[r0 + lane] : item_index_base;
-        const float ibv = (item_bias && lane < nr) ? item_bias[item - item_index_base] : 0.f;   // rides with the row loads
-        __builtin_amdgcn_wave_barrier();
-        if (lane < nr) {
-            const float* b = rows + lane * rstride;
-            float acc = 0.0f;
-            int kk = 0;
-            {
-                for (; kk + 4 <= kdim; kk += 4) {
-                    const f32x4 a4 = *(const f32x4*)(a + kk);
-                    const f32x4 b4 = *(const f32x4*)(b + kk);
-                    acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-                    acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-                }
-            }
-            for (; kk < kdim; ++kk) acc = __fmaf_rn(a[kk], b[kk], acc);
-            if (has_user_bias) acc = acc + bu;
-            if (item_bias) acc = acc + ibv;
-            key = merge_key(acc, item);
-        } else key = EMPTY;
-        __builtin_amdgcn_wave_barrier();
-        // lane r0 + r takes over lane r's key (r0 is a multiple of 16: a fixed rotation per round)
-        {
-            const int srcl = (lane - r0) & 63;
-            const unsigned int lo = (unsigned int)__shfl((int)(unsigned int)key, srcl, 64);
-            const unsigned int hi = (unsigned int)__shfl((int)(unsigned int)(key >> 32), srcl, 64);
-            if (lane >= r0 && lane < r0 + nr) mine = ((unsigned long long)hi << 32) | lo;
-        }
-    }
-    // ---- the k best by (value desc, index asc)
+    for (int r0 = 0; r0 < total; r0 += FILTER_RB)                 // (r0 is a multiple of FILTER_RB: a fixed rotation per round)
+        finish_stage_round(cand + r0, (total - r0 < FILTER_RB) ? total - r0 : FILTER_RB, r0, mine, urow, rows, lane, kdim, chunks,
+                           rstride, vec, V, ld_v, item_index_base, item_bias, has_user_bias, bu);
     for (int t = 0; t < k; ++t) {
         const unsigned long long best = wave_max_u64(mine);
-        if (mine == best && best != EMPTY) mine = EMPTY;
-        if (lane == 0) {
-            const unsigned int hi = (unsigned int)(best >> 32);
-            const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-            ov[u * k + t] = (best == EMPTY) ? -INFINITY : __uint_as_float(bits);
-            oi[u * k + t] = (best == EMPTY) ? -1 : (int32_t)(~(unsigned int)best);
-        }
+        if (mine == best && best != MERGE_KEY_EMPTY) mine = MERGE_KEY_EMPTY;
+        if (lane == 0) store_place(ov, oi, u * k + t, best);
     }
 }
 
@@ -421,11 +358,11 @@ __global__ __launch_bounds__(256) void filter_finish_kernel(
     const int64_t u = (int64_t)blockIdx.x * 4 + wave;
     if (u >= n_users) return;
     const int lane = lane_id();
-    const int kd4 = (kdim + 3) & ~3;                         // floats staged per row (operand rows are padded to kpad >= kd4)
-    const int rstride = kd4 + 4;                             // +4 floats: lanes r = 0..15 start on distinct 4-bank groups
-    int32_t* cand = (int32_t*)fsmem + wave * FILTER_CMAX;
-    float* urow = (float*)(fsmem + 4 * FILTER_CMAX * 4) + (size_t)wave * kd4;
-    float* rows = (float*)(fsmem + 4 * FILTER_CMAX * 4) + (size_t)4 * kd4 + (size_t)wave * FILTER_RB * rstride;
+    const FinishLds lds(kdim, FILTER_CMAX);
+    const int rstride = lds.rstride();
+    int32_t* cand = lds.queue(fsmem, wave);
+    float* urow = lds.urow(fsmem, wave);
+    float* rows = lds.rows(fsmem, wave);
     // ---- everything that does not depend on anything else leaves at once: the user's count, its row and bias, and --
     // speculatively, before the count is known -- the id lists of its first FILTER_SPEC slots (their entries are masked
     // by the count afterwards; a user with more kept slots pays one more round trip).  The wave is latency-bound: every
@@ -434,8 +371,8 @@ __global__ __launch_bounds__(256) void filter_finish_kernel(
     const int64_t base = u * (int64_t)ksel * 2 * cap;
     const int n_ent = ksel * 2 * cap;
     const int n_spec = (n_ent < FILTER_SPEC * 2 * cap) ? n_ent : FILTER_SPEC * 2 * cap;
-    const int chunks = kd4 >> 2;
-    const bool vec = ((ld_v & 3) == 0) && ((ld_u & 3) == 0);
+    const int chunks = lds.chunks();
+    const bool vec = rows_are_vec4(ld_u, ld_v);
     int32_t id[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
@@ -447,14 +384,7 @@ __global__ __launch_bounds__(256) void filter_finish_kernel(
     for (int q = 0; q < 4; ++q) {
         const int ch = q * 64 + lane;
         uw[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (ch < chunks) {
-            const float* src = U + u * ld_u + ch * 4;
-            if (vec) uw[q] = *(const f32x4*)src;
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) uw[q][e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-            }
-        }
+        if (ch < chunks) uw[q] = load_row_chunk(U + u * ld_u, ch, kdim, vec);
     }
     const float bu = user_bias ? user_bias[u] : 0.f;
     // ---- kept slots: the first count[u] of the user's ksel slots (trec_topk_collect_blocks)
@@ -478,7 +408,7 @@ __global__ __launch_bounds__(256) void filter_finish_kernel(
         total += __builtin_popcountll(m);
     }
     const bool over = __builtin_amdgcn_ballot_w64(lossy) != 0ull || total > FILTER_CMAX;
-    if (over && lane == 0 && flag[u] == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
+    if (over && lane == 0) flag_user(flag, n_flagged, u);
     if (total > FILTER_CMAX) total = FILTER_CMAX;
     finish_rescore_topk(total, cand, urow, rows, uw, lane, kdim, chunks, rstride, vec, V, ld_v, item_index_base, item_bias,
                         user_bias != nullptr, bu, k, ov, oi, u);
@@ -491,6 +421,7 @@ __global__ __launch_bounds__(256) void filter_finish_kernel(
 // batch the running top-k (lanes 0..k-1) and the batch's keys (lanes 16..63) go through k rounds of a DPP wave maximum.
 // Only a FULL stage-3 list (it may have dropped an item above the floor) still flags the user.
 #define WIDE_NEW 48
+#define WIDE_QUEUE 128       // ids queued per wave: at most WIDE_NEW - 1 left over + 64 new ones
 __global__ __launch_bounds__(256) void filter_finish_wide_kernel(
     const int32_t* __restrict__ pi, int cap, int ksel, const int32_t* __restrict__ count, const float* __restrict__ U,
     const float* __restrict__ V, int64_t ld_u, int64_t ld_v, int kdim, const float* __restrict__ user_bias,
@@ -502,30 +433,20 @@ __global__ __launch_bounds__(256) void filter_finish_wide_kernel(
     const int64_t u = (int64_t)blockIdx.x * 4 + wave;
     if (u >= n_users) return;
     const int lane = lane_id();
-    const int kd4 = (kdim + 3) & ~3;
-    const int rstride = kd4 + 4;
-    int32_t* cand = (int32_t*)fsmem + wave * 128;                       // queue: at most 47 left over + 64 new ids
-    float* urow = (float*)(fsmem + 4 * 128 * 4) + (size_t)wave * kd4;
-    float* rows = (float*)(fsmem + 4 * 128 * 4) + (size_t)4 * kd4 + (size_t)wave * FILTER_RB * rstride;
-    const int chunks = kd4 >> 2;
-    const bool vec = ((ld_v & 3) == 0) && ((ld_u & 3) == 0);
+    const FinishLds lds(kdim, WIDE_QUEUE);
+    const int rstride = lds.rstride();
+    int32_t* cand = lds.queue(fsmem, wave);
+    float* urow = lds.urow(fsmem, wave);
+    float* rows = lds.rows(fsmem, wave);
+    const int chunks = lds.chunks();
+    const bool vec = rows_are_vec4(ld_u, ld_v);
     int c_u = count[u];
     if (c_u > ksel) c_u = ksel;
     const int64_t base = u * (int64_t)ksel * 2 * cap;
     const int n_ent = c_u * 2 * cap;                                    // the kept slots are the first count[u] ones
-    for (int ch = lane; ch < chunks; ch += 64) {
-        const float* src = U + u * ld_u + ch * 4;
-        f32x4 w;
-        if (vec) w = *(const f32x4*)src;
-        else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-        }
-        *(f32x4*)(urow + ch * 4) = w;
-    }
+    for (int ch = lane; ch < chunks; ch += 64) *(f32x4*)(urow + ch * 4) = load_row_chunk(U + u * ld_u, ch, kdim, vec);
     const float bu = user_bias ? user_bias[u] : 0.f;
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
-    unsigned long long best = EMPTY;                                    // lane t < k: the t-th best key so far
+    unsigned long long best = MERGE_KEY_EMPTY;                          // lane t < k: the t-th best key so far
     bool lossy = false;
     int queued = 0;
     __builtin_amdgcn_wave_barrier();
@@ -542,52 +463,15 @@ __global__ __launch_bounds__(256) void filter_finish_wide_kernel(
         const bool last = e0 + 64 >= n_ent;
         while (queued >= WIDE_NEW || (last && queued > 0)) {
             const int nb = queued < WIDE_NEW ? queued : WIDE_NEW;
-            unsigned long long mine = (lane < 16) ? best : EMPTY;      // lanes 16 .. 16 + nb - 1 take the batch's keys
-            for (int r0 = 0; r0 < nb; r0 += FILTER_RB) {
-                const int nr = (nb - r0 < FILTER_RB) ? nb - r0 : FILTER_RB;
-                for (int idx = lane; idx < nr * chunks; idx += 64) {
-                    const int r = idx / chunks, ch = idx - r * chunks;
-                    const float* src = V + (int64_t)(cand[r0 + r] - item_index_base) * ld_v + ch * 4;
-                    f32x4 w;
-                    if (vec) w = *(const f32x4*)src;
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) w[e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-                    }
-                    *(f32x4*)(rows + r * rstride + ch * 4) = w;
-                }
-                const int32_t item = (lane < nr) ? cand[r0 + lane] : item_index_base;
-                const float ibv = (item_bias && lane < nr) ? item_bias[item - item_index_base] : 0.f;
-                __builtin_amdgcn_wave_barrier();
-                unsigned long long key = EMPTY;
-                if (lane < nr) {
-                    const float* b = rows + lane * rstride;
-                    float acc = 0.0f;
-                    int kk = 0;
-                    for (; kk + 4 <= kdim; kk += 4) {
-                        const f32x4 a4 = *(const f32x4*)(urow + kk);
-                        const f32x4 b4 = *(const f32x4*)(b + kk);
-                        acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-                        acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-                    }
-                    for (; kk < kdim; ++kk) acc = __fmaf_rn(urow[kk], b[kk], acc);
-                    if (user_bias) acc = acc + bu;
-                    if (item_bias) acc = acc + ibv;
-                    key = merge_key(acc, item);
-                }
-                __builtin_amdgcn_wave_barrier();
-                {   // lane 16 + r0 + r takes over lane r's key
-                    const int srcl = (lane - 16 - r0) & 63;
-                    const unsigned int lo = (unsigned int)__shfl((int)(unsigned int)key, srcl, 64);
-                    const unsigned int hi = (unsigned int)__shfl((int)(unsigned int)(key >> 32), srcl, 64);
-                    if (lane >= 16 + r0 && lane < 16 + r0 + nr) mine = ((unsigned long long)hi << 32) | lo;
-                }
-            }
+            unsigned long long mine = (lane < 16) ? best : MERGE_KEY_EMPTY;      // lanes 16 .. 16 + nb - 1 take the batch's keys
+            for (int r0 = 0; r0 < nb; r0 += FILTER_RB)
+                finish_stage_round(cand + r0, (nb - r0 < FILTER_RB) ? nb - r0 : FILTER_RB, 16 + r0, mine, urow, rows, lane, kdim, chunks,
+                                   rstride, vec, V, ld_v, item_index_base, item_bias, user_bias != nullptr, bu);
             // the k best of (running top-k, this batch): keys are unique (an item sits in exactly one list)
-            unsigned long long nxt = EMPTY;
+            unsigned long long nxt = MERGE_KEY_EMPTY;
             for (int t = 0; t < k; ++t) {
                 const unsigned long long b = wave_max_u64(mine);
-                if (mine == b && b != EMPTY) mine = EMPTY;
+                if (mine == b && b != MERGE_KEY_EMPTY) mine = MERGE_KEY_EMPTY;
                 if (lane == t) nxt = b;
             }
             best = nxt;
@@ -600,17 +484,12 @@ __global__ __launch_bounds__(256) void filter_finish_wide_kernel(
             queued = rest;
         }
     }
-    if (__builtin_amdgcn_ballot_w64(lossy) != 0ull && lane == 0 && flag[u] == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
-    if (lane < k) {
-        const unsigned int hi = (unsigned int)(best >> 32);
-        const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-        ov[u * k + lane] = (best == EMPTY) ? -INFINITY : __uint_as_float(bits);
-        oi[u * k + lane] = (best == EMPTY) ? -1 : (int32_t)(~(unsigned int)best);
-    }
+    if (__builtin_amdgcn_ballot_w64(lossy) != 0ull && lane == 0) flag_user(flag, n_flagged, u);
+    if (lane < k) store_place(ov, oi, u * k + lane, best);
 }
 
 
-// ---- the finish behind the cascade's candidate lists (csrc/topk_candidates.hip) ---------------------------------------------
+// ---- the finish behind the cascade's candidate lists (the LIST form of csrc/score_blockmax.hip) ------------------------------
 // One wave per user.  cand[u][0 .. n) = {item id, bf16-path score sh} of EVERY item of the user's refined superblocks with
 // sh >= cand_floor[u] (blockmax_bf16x16_kernel<.., LIST>).  tau = the k-th largest sh among them, floor = tau - 2 eps (the
 // filter's floor, from item scores instead of superblock maxima), survivors = candidates with sh >= floor, re-scored exactly.
@@ -632,16 +511,16 @@ __device__ __forceinline__ void candidates_finish_user(
     const int64_t uo = out_index ? (int64_t)out_index[u] : u;
     if (uo < 0) return;                                     // (wave-uniform)
     const int lane = lane_id();
-    const int kd4 = (kdim + 3) & ~3;
-    const int rstride = kd4 + 4;
-    int32_t* cand = (int32_t*)fsmem + wave * FILTER_CMAX;
-    float* urow = (float*)(fsmem + 4 * FILTER_CMAX * 4) + (size_t)wave * kd4;
-    float* rows = (float*)(fsmem + 4 * FILTER_CMAX * 4) + (size_t)4 * kd4 + (size_t)wave * FILTER_RB * rstride;
+    const FinishLds lds(kdim, FILTER_CMAX);
+    const int rstride = lds.rstride();
+    int32_t* cand = lds.queue(fsmem, wave);
+    float* urow = lds.urow(fsmem, wave);
+    float* rows = lds.rows(fsmem, wave);
     // everything that depends on nothing leaves at once: the count, the floor, the list (masked by the count afterwards), the row
     const int n = cand_n[u];
     const float f0 = cand_floor[u];
-    const int chunks = kd4 >> 2;
-    const bool vec = ((ld_v & 3) == 0) && ((ld_u & 3) == 0);
+    const int chunks = lds.chunks();
+    const bool vec = rows_are_vec4(ld_u, ld_v);
     int2 ent[CPL];                                          // the first 64 entries before the count is known (a user has ~32), the rest after
     ent[0] = cand_list[u * (int64_t)cap + lane];
     f32x4 uw[4];
@@ -649,18 +528,10 @@ __device__ __forceinline__ void candidates_finish_user(
     for (int q = 0; q < 4; ++q) {
         const int ch = q * 64 + lane;
         uw[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (ch < chunks) {
-            const float* src = U + u * ld_u + ch * 4;
-            if (vec) uw[q] = *(const f32x4*)src;
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) uw[q][e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-            }
-        }
+        if (ch < chunks) uw[q] = load_row_chunk(U + u * ld_u, ch, kdim, vec);
     }
     const float bu = user_bias ? user_bias[u] : 0.f;
     const float2 st = ustats[u];
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
     const bool skip = !(f0 < INFINITY);
     const bool over = n > cap;
 #pragma unroll
@@ -669,35 +540,27 @@ __device__ __forceinline__ void candidates_finish_user(
         if (n > c * 64 && !over) ent[c] = cand_list[u * (int64_t)cap + c * 64 + lane];
     }
     if (skip || over) {                                     // (wave-uniform)
-        if (over && !skip && lane == 0 && flag[u] == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
-        if (lane < k) { ov[uo * k + lane] = -INFINITY; oi[uo * k + lane] = -1; }
+        if (over && !skip && lane == 0) flag_user(flag, n_flagged, u);
+        if (lane < k) store_place(ov, oi, uo * k + lane, MERGE_KEY_EMPTY);
         return;
     }
     // ---- tau = the k-th largest candidate score (keys: value desc, id asc -- an item is listed once, keys are unique)
     unsigned long long key[CPL], w[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-        key[c] = (c * 64 + lane < n) ? merge_key(__int_as_float(ent[c].y), ent[c].x) : EMPTY;
+        key[c] = (c * 64 + lane < n) ? merge_key(__int_as_float(ent[c].y), ent[c].x) : MERGE_KEY_EMPTY;
         w[c] = key[c];
     }
-    unsigned long long kth = EMPTY;
+    unsigned long long kth = MERGE_KEY_EMPTY;
     for (int t = 0; t < k; ++t) {
         unsigned long long m = w[0];
 #pragma unroll
         for (int c = 1; c < CPL; ++c) m = w[c] > m ? w[c] : m;
         kth = wave_max_u64(m);
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) if (w[c] == kth && kth != EMPTY) w[c] = EMPTY;
+        for (int c = 0; c < CPL; ++c) if (w[c] == kth && kth != MERGE_KEY_EMPTY) w[c] = MERGE_KEY_EMPTY;
     }
-    float tau = -INFINITY;                                  // fewer than k candidates: every one survives
-    if (kth != EMPTY) {
-        const unsigned int hi = (unsigned int)(kth >> 32);
-        tau = __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
-    }
-    const float eps = filter_eps(st, fabsf(bu), gstats, kdim);
-    float fl = tau - 2.0f * eps;
-    if (tau == -INFINITY) fl = -INFINITY;
-    else fl = float_pred(float_pred(fl));                   // (eps is finite here: cand_floor was)
+    const float fl = finish_floor_from_kth(kth, filter_eps(st, fabsf(bu), gstats, kdim));    // (eps is finite here: cand_floor was)
     // ---- survivors
     int total = 0;
 #pragma unroll
@@ -709,7 +572,7 @@ __device__ __forceinline__ void candidates_finish_user(
         total += __builtin_popcountll(m);
     }
     if (total > FILTER_CMAX) {
-        if (lane == 0 && flag[u] == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
+        if (lane == 0) flag_user(flag, n_flagged, u);
         total = FILTER_CMAX;
     }
     finish_rescore_topk(total, cand, urow, rows, uw, lane, kdim, chunks, rstride, vec, V, ld_v, item_index_base, item_bias,
@@ -779,8 +642,7 @@ __global__ __launch_bounds__(256) void candidates_finish16_kernel(
     extern __shared__ __attribute__((aligned(16))) char fsmem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane >> 4, gl = lane & 15;
-    const int kd4 = (kdim + 3) & ~3;
-    float* urow = (float*)fsmem + (size_t)(wave * 4 + grp) * kd4;           // this user's fp32 row, read by its 16 lanes
+    float* urow = finish_user_row(fsmem, wave * 4 + grp, kdim);            // this user's fp32 row, read by its 16 lanes
     const int64_t u = ((int64_t)blockIdx.x * 4 + wave) * 4 + grp;
     const bool live = u < n_users;
     const int64_t uc = live ? u : n_users - 1;
@@ -790,92 +652,58 @@ __global__ __launch_bounds__(256) void candidates_finish16_kernel(
     int2 ent[CPL];                                           // (unconditional loads inside the list's capacity, masked by the count)
 #pragma unroll
     for (int c = 0; c < CPL; ++c) ent[c] = cand_list[uc * (int64_t)cap + (gl + 16 * c < cap ? gl + 16 * c : cap - 1)];
-    const bool vec = ((ld_v & 3) == 0) && ((ld_u & 3) == 0);
-    for (int ch = gl; ch < (kd4 >> 2); ch += 16) {
-        f32x4 w = {0.f, 0.f, 0.f, 0.f};
-        const float* src = U + uc * ld_u + ch * 4;
-        if (vec) w = *(const f32x4*)src;
-        else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-        }
-        *(f32x4*)(urow + ch * 4) = w;
-    }
+    const bool vec = rows_are_vec4(ld_u, ld_v);
+    for (int ch = gl; ch < (finish_kd4(kdim) >> 2); ch += 16) *(f32x4*)(urow + ch * 4) = load_row_chunk(U + uc * ld_u, ch, kdim, vec);
     const float bu = user_bias ? user_bias[uc] : 0.f;
     const float2 st = ustats[uc];
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
     const bool skip = !live || uo < 0 || !(f0 < INFINITY);                 // (uniform over the 16 lanes of the user)
     const bool over = n > 16 * CPL || n > cap;
     // ---- tau = the k-th largest listed score of this user (row maxima: nothing crosses the 16-lane rows)
     unsigned long long wkey[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c)
-        wkey[c] = (!skip && !over && gl + 16 * c < n) ? merge_key(__int_as_float(ent[c].y), ent[c].x) : EMPTY;
-    unsigned long long kth = EMPTY;
+        wkey[c] = (!skip && !over && gl + 16 * c < n) ? merge_key(__int_as_float(ent[c].y), ent[c].x) : MERGE_KEY_EMPTY;
+    unsigned long long kth = MERGE_KEY_EMPTY;
     for (int t = 0; t < k; ++t) {
         unsigned long long m = wkey[0];
 #pragma unroll
         for (int c = 1; c < CPL; ++c) m = wkey[c] > m ? wkey[c] : m;
         kth = row16_max_u64(m);
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) if (wkey[c] == kth && kth != EMPTY) wkey[c] = EMPTY;
+        for (int c = 0; c < CPL; ++c) if (wkey[c] == kth && kth != MERGE_KEY_EMPTY) wkey[c] = MERGE_KEY_EMPTY;
     }
-    float tau = -INFINITY;
-    if (kth != EMPTY) {
-        const unsigned int hi = (unsigned int)(kth >> 32);
-        tau = __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
-    }
-    const float eps = filter_eps(st, fabsf(bu), gstats, kdim);
-    float fl = tau - 2.0f * eps;
-    if (tau == -INFINITY) fl = -INFINITY;
-    else fl = float_pred(float_pred(fl));
+    const float fl = finish_floor_from_kth(kth, filter_eps(st, fabsf(bu), gstats, kdim));
     __builtin_amdgcn_wave_barrier();                                       // urow is private to this wave: DS operations of a wave execute in order
     // ---- exact fp32 score of this lane's candidates: the reference's k-ordered fmaf chain, then (s + b_u) + b_i
     unsigned long long mine[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
         const bool keep = !skip && !over && gl + 16 * c < n && __int_as_float(ent[c].y) >= fl;
-        mine[c] = EMPTY;
+        mine[c] = MERGE_KEY_EMPTY;
         if (c > 0 && __builtin_amdgcn_ballot_w64(keep) == 0ull) continue;   // (wave-uniform: nobody holds a survivor in this slot)
         const int64_t it = keep ? (int64_t)ent[c].x - item_index_base : 0;
-        const float* b = V + it * ld_v;
-        float acc = 0.0f;
-        int kk = 0;
-        if (vec) {
-            for (; kk + 4 <= kdim; kk += 4) {
-                const f32x4 a4 = *(const f32x4*)(urow + kk);
-                const f32x4 b4 = *(const f32x4*)(b + kk);
-                acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-                acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-            }
-        }
-        for (; kk < kdim; ++kk) acc = __fmaf_rn(urow[kk], b[kk], acc);
+        float acc = exact_chain(0.0f, urow, V + it * ld_v, kdim, vec);
         if (user_bias) acc = acc + bu;
         if (item_bias) acc = acc + item_bias[it];
         if (keep) mine[c] = merge_key(acc, ent[c].x);
     }
     // ---- the k best by (value desc, index asc): lane t of the user's row writes place t
-    unsigned long long place = EMPTY;
+    unsigned long long place = MERGE_KEY_EMPTY;
     for (int t = 0; t < k; ++t) {
         unsigned long long m = mine[0];
 #pragma unroll
         for (int c = 1; c < CPL; ++c) m = mine[c] > m ? mine[c] : m;
         const unsigned long long best = row16_max_u64(m);
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) if (mine[c] == best && best != EMPTY) mine[c] = EMPTY;
+        for (int c = 0; c < CPL; ++c) if (mine[c] == best && best != MERGE_KEY_EMPTY) mine[c] = MERGE_KEY_EMPTY;
         if (gl == t) place = best;
     }
     if (live && uo >= 0) {
         const bool handed_on = over && !skip && over_list != nullptr;      // the listed kernel writes this user's rows
-        if (gl < k && !handed_on) {
-            const unsigned int hi = (unsigned int)(place >> 32);
-            const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-            ov[uo * k + gl] = (place == EMPTY) ? -INFINITY : __uint_as_float(bits);
-            oi[uo * k + gl] = (place == EMPTY) ? -1 : (int32_t)(~(unsigned int)place);
-        }
+        if (gl < k && !handed_on) store_place(ov, oi, uo * k + gl, place);
         if (over && !skip && gl == 0) {
             if (over_list) over_list[atomicAdd(over_count, 1)] = (int32_t)u;
-            else if (flag[u] == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
+            else flag_user(flag, n_flagged, u);
         }
     }
 }
@@ -936,14 +764,12 @@ extern "C" int trec_topk_filter_finish(const int32_t* part_idx, int32_t capacity
                  "trec_topk_filter_finish: null pointer");
     TREC_REQUIRE(ksel >= 1 && ksel <= 64 && k >= 1 && k <= FILTER_CMAX, "trec_topk_filter_finish: need ksel <= 64, k <= 64");
     TREC_REQUIRE(capacity >= 1 && ksel * 2 * capacity <= 64 * 32, "trec_topk_filter_finish: ksel * 2 * capacity <= 2048");
-    TREC_REQUIRE(kdim >= 1 && kdim <= 1024 && ld_users >= kdim && ld_items >= ((kdim + 3) & ~3),
-                 "trec_topk_filter_finish: need kdim <= 1024 and item rows padded to a multiple of 4");
+    if (const int rc = finish_check_operands("trec_topk_filter_finish", kdim, ld_users, ld_items)) return rc;
     if (n_users == 0) return TREC_OK;
     const unsigned blocks = (unsigned)ceil_div64(n_users, 4);
     hipStream_t st = (hipStream_t)stream;
     const int cpl = (ksel * 2 * capacity + 63) / 64;
-    const int kd4 = (kdim + 3) & ~3;
-    const size_t lds = 4 * FILTER_CMAX * 4 + (size_t)4 * kd4 * 4 + (size_t)4 * FILTER_RB * (kd4 + 4) * 4;
+    const size_t lds = FinishLds(kdim, FILTER_CMAX).bytes();
 #define TREC_FF(CPLV)                                                                                                  \
     (void)hipFuncSetAttribute((const void*)filter_finish_kernel<CPLV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     hipLaunchKernelGGL((filter_finish_kernel<CPLV>), dim3(blocks), dim3(256), lds, st, part_idx, capacity, ksel, count, \
@@ -969,11 +795,9 @@ extern "C" int trec_topk_filter_finish_wide(const int32_t* part_idx, int32_t cap
     TREC_REQUIRE(part_idx && count && users_f32 && items_f32 && out_vals && out_idx && flag && n_flagged,
                  "trec_topk_filter_finish_wide: null pointer");
     TREC_REQUIRE(ksel >= 1 && k >= 1 && k <= 16 && capacity >= 1, "trec_topk_filter_finish_wide: need k <= 16");
-    TREC_REQUIRE(kdim >= 1 && kdim <= 1024 && ld_users >= kdim && ld_items >= ((kdim + 3) & ~3),
-                 "trec_topk_filter_finish_wide: need kdim <= 1024 and item rows padded to a multiple of 4");
+    if (const int rc = finish_check_operands("trec_topk_filter_finish_wide", kdim, ld_users, ld_items)) return rc;
     if (n_users == 0) return TREC_OK;
-    const int kd4 = (kdim + 3) & ~3;
-    const size_t lds = 4 * 128 * 4 + (size_t)4 * kd4 * 4 + (size_t)4 * FILTER_RB * (kd4 + 4) * 4;
+    const size_t lds = FinishLds(kdim, WIDE_QUEUE).bytes();
     (void)hipFuncSetAttribute((const void*)filter_finish_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(filter_finish_wide_kernel, dim3((unsigned)ceil_div64(n_users, 4)), dim3(256), lds, (hipStream_t)stream,
                        part_idx, capacity, ksel, count, users_f32, items_f32, ld_users, ld_items, kdim, user_bias, item_bias,
@@ -999,15 +823,13 @@ extern "C" int trec_topk_candidates_finish(const int32_t* cand_n, const void* ca
                  flag && n_flagged, "trec_topk_candidates_finish: null pointer");
     TREC_REQUIRE(cand_cap >= 64 && cand_cap % 64 == 0 && cand_cap <= 256, "trec_topk_candidates_finish: cand_cap must be 64, 128, 192 or 256");
     TREC_REQUIRE(k >= 1 && k <= 16, "trec_topk_candidates_finish: need k <= 16");
-    TREC_REQUIRE(kdim >= 1 && kdim <= 1024 && ld_users >= kdim && ld_items >= ((kdim + 3) & ~3),
-                 "trec_topk_candidates_finish: need kdim <= 1024 and item rows padded to a multiple of 4");
+    if (const int rc = finish_check_operands("trec_topk_candidates_finish", kdim, ld_users, ld_items)) return rc;
     if (n_users == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int kd4 = (kdim + 3) & ~3;
     if (lanes_per_user == 16) {
         // short lists (item shards): 16 lanes per user, 16 users per workgroup; users with more than 16 candidates are flagged
         TREC_REQUIRE(k <= 16, "trec_topk_candidates_finish: the 16-lane form needs k <= 16");
-        const size_t lds16 = (size_t)16 * kd4 * 4;
+        const size_t lds16 = finish_user_rows_bytes(kdim, 16);
         hipLaunchKernelGGL(candidates_finish16_kernel<1>, dim3((unsigned)ceil_div64(n_users, 16)), dim3(256), lds16, st, cand_n,
                            (const int2*)cand, cand_cap, cand_floor, (const float2*)user_stats, item_gstats, users_f32, items_f32,
                            ld_users, ld_items, kdim, user_bias, item_bias, item_index_base, n_users, k, out_vals, out_idx, flag,
@@ -1015,7 +837,7 @@ extern "C" int trec_topk_candidates_finish(const int32_t* cand_n, const void* ca
         return trec_check_launch("trec_topk_candidates_finish (16 lanes per user)");
     }
     const unsigned blocks = (unsigned)ceil_div64(n_users, 4);
-    const size_t lds = 4 * FILTER_CMAX * 4 + (size_t)4 * kd4 * 4 + (size_t)4 * FILTER_RB * (kd4 + 4) * 4;
+    const size_t lds = FinishLds(kdim, FILTER_CMAX).bytes();
 #define TREC_CF(CPLV)                                                                                                  \
     (void)hipFuncSetAttribute((const void*)candidates_finish_kernel<CPLV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     hipLaunchKernelGGL((candidates_finish_kernel<CPLV>), dim3(blocks), dim3(256), lds, st, cand_n, (const int2*)cand, cand_cap, \
@@ -1049,73 +871,46 @@ __global__ __launch_bounds__(256) void candidates_finish_wide_kernel(
     if (u >= n_users) return;
     const int64_t uo = out_index ? (int64_t)out_index[u] : u;
     if (uo < 0) return;
-    const int kd4 = (kdim + 3) & ~3;
-    float* urow = (float*)fsmem + (size_t)wave * kd4;
+    float* urow = finish_user_row(fsmem, wave, kdim);
     const int n = cand_n[u];
     const float f0 = cand_floor[u];
-    const bool vec = ((ld_v & 3) == 0) && ((ld_u & 3) == 0);
-    for (int ch = lane; ch < (kd4 >> 2); ch += 64) {
-        f32x4 w = {0.f, 0.f, 0.f, 0.f};
-        const float* src = U + u * ld_u + ch * 4;
-        if (vec) w = *(const f32x4*)src;
-        else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = (ch * 4 + e < kdim) ? src[e] : 0.f;
-        }
-        *(f32x4*)(urow + ch * 4) = w;
-    }
+    const bool vec = rows_are_vec4(ld_u, ld_v);
+    for (int ch = lane; ch < (finish_kd4(kdim) >> 2); ch += 64) *(f32x4*)(urow + ch * 4) = load_row_chunk(U + u * ld_u, ch, kdim, vec);
     const float bu = user_bias ? user_bias[u] : 0.f;
-    const unsigned long long EMPTY = merge_key(-INFINITY, 0x7fffffff);
     const bool skip = !(f0 < INFINITY) || flag[u] != 0;      // (wave-uniform)
     const bool bad = n > cap || n < k;
     if (skip || bad) {
-        if (bad && !skip && lane == 0) { flag[u] = 1; atomicAdd(n_flagged, 1); }
-        if (lane < k) { ov[uo * k + lane] = -INFINITY; oi[uo * k + lane] = -1; }
+        if (bad && !skip && lane == 0) flag_user(flag, n_flagged, u);
+        if (lane < k) store_place(ov, oi, uo * k + lane, MERGE_KEY_EMPTY);
         return;
     }
     __builtin_amdgcn_wave_barrier();
     unsigned long long key[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-        key[c] = EMPTY;
+        key[c] = MERGE_KEY_EMPTY;
         if (c * 64 >= n) continue;                            // (wave-uniform)
         const bool have = c * 64 + lane < n;
         const int2 ent = cand_list[u * (int64_t)cap + (have ? c * 64 + lane : 0)];
         const int64_t it = (int64_t)ent.x - item_index_base;
-        const float* b = V + it * ld_v;
-        float acc = 0.0f;
-        int kk = 0;
-        if (vec) {
-            for (; kk + 4 <= kdim; kk += 4) {
-                const f32x4 a4 = *(const f32x4*)(urow + kk);
-                const f32x4 b4 = *(const f32x4*)(b + kk);
-                acc = __fmaf_rn(a4[0], b4[0], acc); acc = __fmaf_rn(a4[1], b4[1], acc);
-                acc = __fmaf_rn(a4[2], b4[2], acc); acc = __fmaf_rn(a4[3], b4[3], acc);
-            }
-        }
-        for (; kk < kdim; ++kk) acc = __fmaf_rn(urow[kk], b[kk], acc);
+        float acc = exact_chain(0.0f, urow, V + it * ld_v, kdim, vec);
         if (user_bias) acc = acc + bu;
         if (item_bias) acc = acc + item_bias[it];
         if (have) key[c] = merge_key(acc, ent.x);
     }
     // ---- the k best by (value desc, index asc): lane t keeps place t (an item is listed once: keys are unique, and equal keys -- the
     // harmless double listing of a pre-refined pair inside a hot superblock -- leave together)
-    unsigned long long place = EMPTY;
+    unsigned long long place = MERGE_KEY_EMPTY;
     for (int t = 0; t < k; ++t) {
         unsigned long long m = key[0];
 #pragma unroll
         for (int c = 1; c < CPL; ++c) m = key[c] > m ? key[c] : m;
         const unsigned long long best = wave_max_u64(m);
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) if (key[c] == best && best != EMPTY) key[c] = EMPTY;
+        for (int c = 0; c < CPL; ++c) if (key[c] == best && best != MERGE_KEY_EMPTY) key[c] = MERGE_KEY_EMPTY;
         if (lane == t) place = best;
     }
-    if (lane < k) {
-        const unsigned int hi = (unsigned int)(place >> 32);
-        const unsigned int bits = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-        ov[uo * k + lane] = (place == EMPTY) ? -INFINITY : __uint_as_float(bits);
-        oi[uo * k + lane] = (place == EMPTY) ? -1 : (int32_t)(~(unsigned int)place);
-    }
+    if (lane < k) store_place(ov, oi, uo * k + lane, place);
 }
 
 extern "C" int trec_topk_candidates_finish_wide(const int32_t* cand_n, const void* cand, int32_t cand_cap, const float* cand_floor,
@@ -1128,12 +923,10 @@ extern "C" int trec_topk_candidates_finish_wide(const int32_t* cand_n, const voi
                  "trec_topk_candidates_finish_wide: null pointer");
     TREC_REQUIRE(cand_cap >= 64 && cand_cap % 64 == 0 && cand_cap <= 1024, "trec_topk_candidates_finish_wide: cand_cap must be a multiple of 64 up to 1024");
     TREC_REQUIRE(k >= 1 && k <= 64, "trec_topk_candidates_finish_wide: need k <= 64");
-    TREC_REQUIRE(kdim >= 1 && kdim <= 1024 && ld_users >= kdim && ld_items >= ((kdim + 3) & ~3),
-                 "trec_topk_candidates_finish_wide: need kdim <= 1024 and item rows padded to a multiple of 4");
+    if (const int rc = finish_check_operands("trec_topk_candidates_finish_wide", kdim, ld_users, ld_items)) return rc;
     if (n_users == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int kd4 = (kdim + 3) & ~3;
-    const size_t lds = (size_t)4 * kd4 * 4;
+    const size_t lds = finish_user_rows_bytes(kdim, 4);
     const unsigned blocks = (unsigned)ceil_div64(n_users, 4);
 #define TREC_CFW(CPLV)                                                                                                          \
     hipLaunchKernelGGL((candidates_finish_wide_kernel<CPLV>), dim3(blocks), dim3(256), lds, st, cand_n, (const int2*)cand, cand_cap, \
@@ -1163,12 +956,11 @@ extern "C" int trec_topk_candidates_finish_mixed(const int32_t* cand_n, const vo
                  flag && n_flagged && over_list && over_count, "trec_topk_candidates_finish_mixed: null pointer");
     TREC_REQUIRE(cand_cap >= 64 && cand_cap % 64 == 0 && cand_cap <= 256, "trec_topk_candidates_finish_mixed: cand_cap must be 64, 128, 192 or 256");
     TREC_REQUIRE(k >= 1 && k <= 16, "trec_topk_candidates_finish_mixed: need k <= 16");
-    TREC_REQUIRE(kdim >= 1 && kdim <= 1024 && ld_users >= kdim && ld_items >= ((kdim + 3) & ~3) && n_users < ((int64_t)1 << 31),
-                 "trec_topk_candidates_finish_mixed: need kdim <= 1024, item rows padded to a multiple of 4, n_users < 2^31");
+    if (const int rc = finish_check_operands("trec_topk_candidates_finish_mixed", kdim, ld_users, ld_items)) return rc;
+    TREC_REQUIRE(n_users < ((int64_t)1 << 31), "trec_topk_candidates_finish_mixed: need n_users < 2^31");
     if (n_users == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int kd4 = (kdim + 3) & ~3;
-    const size_t lds16 = (size_t)16 * kd4 * 4;
+    const size_t lds16 = finish_user_rows_bytes(kdim, 16);
 #define TREC_CF16(CPLV)                                                                                                         \
     hipLaunchKernelGGL(candidates_finish16_kernel<CPLV>, dim3((unsigned)ceil_div64(n_users, 16)), dim3(256), lds16, st, cand_n,  \
                        (const int2*)cand, cand_cap, cand_floor, (const float2*)user_stats, item_gstats, users_f32, items_f32,    \
@@ -1178,7 +970,7 @@ extern "C" int trec_topk_candidates_finish_mixed(const int32_t* cand_n, const vo
 #undef TREC_CF16
     const int64_t want = ceil_div64(n_users, 4 * 64);                    // (a wave of the listed kernel per ~64 users: lists that long are rare)
     const unsigned blocks = (unsigned)(want < 64 ? 64 : (want > 4096 ? 4096 : want));
-    const size_t lds = 4 * FILTER_CMAX * 4 + (size_t)4 * kd4 * 4 + (size_t)4 * FILTER_RB * (kd4 + 4) * 4;
+    const size_t lds = FinishLds(kdim, FILTER_CMAX).bytes();
 #define TREC_CFL(CPLV)                                                                                                          \
     (void)hipFuncSetAttribute((const void*)candidates_finish_listed_kernel<CPLV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     hipLaunchKernelGGL((candidates_finish_listed_kernel<CPLV>), dim3(blocks), dim3(256), lds, st, (const int32_t*)over_list,      \
