@@ -8,10 +8,7 @@ the first k non-excluded items are usually inside its list, never more than that
 import numpy as np
 import scipy.sparse as sp
 
-# largest k each fused route accepts: over-fetching stays inside the route family that k selected
-ROUTE_FETCH_CAP = {"direct": 16, "two_stage": 16, "cascade_int8": 16, "bf16_filter": 16, "wide_cascade": 64}
-EUCLID_NARROW_CAP = 12       # euclid_certified for k <= 12 (the cascade's 16 fused candidates)
-EUCLID_WIDE_CAP = 48         # ... and through the wide cascade's lists, 13 <= k <= 48
+from . import topk_plan
 
 
 def exclusion_csr(exclude, n_users, n_items):
@@ -46,13 +43,9 @@ def exclusion_csr(exclude, n_users, n_items):
 
 
 def fetch_cap(route, k):
-    """Largest k the route ``route`` (predict_top_k's last_route["route"] for this k) accepts; None for the slab route, which
-    masks its score slabs directly and fetches nothing extra."""
-    if route == "slab":
-        return None
-    if route == "euclid_certified":
-        return EUCLID_NARROW_CAP if int(k) <= EUCLID_NARROW_CAP else EUCLID_WIDE_CAP
-    return ROUTE_FETCH_CAP[route]
+    """Largest k the route ``route`` (predict_top_k's last_route["route"] for this k) accepts -- over-fetching stays inside the
+    route family that k selected; None for the slab route, which masks its score slabs directly and fetches nothing extra."""
+    return topk_plan.route_cap(route, k)
 
 
 def fetch_k(route, k, max_excluded):

@@ -153,6 +153,7 @@ def topk_chunks_for(n_users, dtype, kpad, n_items):
 
 TWO_STAGE_MIN_ITEMS = 16384      # below this the direct fused kernel is cheaper than the extra passes
 SUPERBLOCK_ROWS = 512
+FUSED_K_MAX = 16                 # entries of the fused kernels' per-lane lists: the largest k of score_topk / score_topk_filtered
 
 
 def score_topk(users_op, items_op, dtype, kpad, k, user_bias=None, item_bias=None, mode=MODE_DOT, user_sq=None,
@@ -492,9 +493,9 @@ def topk_user_batch(n_users, n_items, n_components, device, fraction=0.6, route=
     return int(max(65536, min(int(n_users), TOPK_USER_BATCH_MAX, fraction * free / per_user)))
 
 
-def cascade_prefilter_for(n_components, n_items_total):
-    """"int8" when the int8 pre-filter is worth trying for this shape (tuning ``topk_int8_prefilter``, default on), else None."""
-    if N.load().trec_get_tuning(b"topk_int8_prefilter", 1) == 0:
+def cascade_prefilter_for(n_components, n_items_total, enabled=None):
+    """"int8" when the int8 pre-filter is worth trying for this shape, else None (``enabled``: tuning ``topk_int8_prefilter``, None reads it)."""
+    if not (N.load().trec_get_tuning(b"topk_int8_prefilter", 1) != 0 if enabled is None else enabled):
         return None
     return "int8" if score_kpad(n_components) in (64, 128) and n_items_total >= CASCADE_MIN_ITEMS else None
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import logging
 import math
+from collections import namedtuple
 import os
 import pickle
 from itertools import cycle
@@ -27,6 +28,7 @@ from scipy import sparse as sp
 
 from . import ops
 from . import exclusion as _excl
+from . import topk_plan
 from . import similar as _sim
 from . import candidate_sets as _cand
 from . import _native as N
@@ -47,6 +49,9 @@ from .util import calculate_batched_alpha, sample_items
 
 ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults [external]
 PREDICT_CACHE_MAX_NNZ = 200_000_000     # non-zeros of feature matrices the predict* calls keep uploaded (~4 GB of device memory)
+# item side of one exact top-k call: representation, bias or None, global id of the first row, the prepared operand -- the filter
+# operand on the filtered / wide paths, score_prep's (operand, squared norms, kpad) on the others
+_TopkItems = namedtuple("_TopkItems", "repr bias offset op")
 
 
 class DeviceSampler(object):
@@ -1143,25 +1148,18 @@ class TensorRec(object):
                 if want_sq and u_op.shape[1] != kpad:          # (score_prep returns the representation itself when d == kpad)
                     raise RuntimeError("score_prep returned an unpadded operand")
                 pair_indptr = np.searchsorted(rows, np.arange(n_users + 1)).astype(np.int64)
+                ops_ = (u_op, i_op, kpad, user_reprs[0].shape[1])
+                chain = (user_bias.contiguous() if self.biased else None, item_bias.contiguous() if self.biased else None,
+                         graph.engine_mode, u_sq, i_sq)
+                xi_d = torch.from_numpy(np.ascontiguousarray(cols)).to(device)
                 if ex is None:
-                    counts = ops.rank_counts_fused(u_op, i_op, kpad, user_reprs[0].shape[1], pair_indptr,
-                                                   torch.from_numpy(np.ascontiguousarray(cols)).to(device),
-                                                   user_bias.contiguous() if self.biased else None,
-                                                   item_bias.contiguous() if self.biased else None, graph.engine_mode,
-                                                   u_sq, i_sq)
+                    counts = ops.rank_counts_fused(*ops_, pair_indptr, xi_d, *chain)
                 else:
                     # the excluded items' scores and the targets' from the chain K2r compares with (trec_pair_score_exact)
-                    d = user_reprs[0].shape[1]
-                    ubc = user_bias.contiguous() if self.biased else None
-                    ibc = item_bias.contiguous() if self.biased else None
-                    xi_d = torch.from_numpy(np.ascontiguousarray(cols)).to(device)
-                    tgt = ops.pair_scores_exact(u_op, i_op, kpad, d, torch.from_numpy(rows).to(device), xi_d, ubc, ibc,
-                                                graph.engine_mode, u_sq, i_sq)
-                    counts = ops.rank_counts_fused(u_op, i_op, kpad, d, pair_indptr, xi_d, ubc, ibc, graph.engine_mode, u_sq, i_sq,
-                                                   target_scores=tgt)
+                    tgt = ops.pair_scores_exact(*ops_, torch.from_numpy(rows).to(device), xi_d, *chain)
+                    counts = ops.rank_counts_fused(*ops_, pair_indptr, xi_d, *chain, target_scores=tgt)
                     ex_idx_d = torch.from_numpy(ex[1]).to(device)
-                    ex_score = ops.pair_scores_exact(u_op, i_op, kpad, d, torch.from_numpy(ex[2]).to(device), ex_idx_d, ubc, ibc,
-                                                     graph.engine_mode, u_sq, i_sq)
+                    ex_score = ops.pair_scores_exact(*ops_, torch.from_numpy(ex[2]).to(device), ex_idx_d, *chain)
                     ops.exclude_rank_adjust(torch.from_numpy(pair_indptr).to(device), xi_d, tgt,
                                             torch.from_numpy(ex[0]).to(device), ex_idx_d, ex_score, counts)
                 return PairRanks(rows, (counts + 1).cpu().numpy(), vals, n_users)
@@ -1170,14 +1168,7 @@ class TensorRec(object):
                 if p0 == p1:
                     continue
                 e = min(s + user_batch_size, n_users)
-                ub = user_bias[s:e] if user_bias is not None else None
-                if self._multi():
-                    slab = self._dense_multi([u[s:e] for u in user_reprs],
-                                             [a[s:e] for a in attn_reprs] if attn_reprs is not None else None,
-                                             item_repr, ub, item_bias)
-                else:
-                    slab = self._dense_prediction(user_reprs[0][s:e], item_repr, ub, item_bias)
-                slab = slab.contiguous()
+                slab = self._score_slab(user_reprs, attn_reprs, item_repr, user_bias, item_bias, rows=slice(s, e)).contiguous()
                 xi32 = torch.from_numpy(cols[p0:p1]).to(device)
                 xu = (torch.from_numpy(rows[p0:p1]).to(device) - s).long()
                 xi = xi32.long()
@@ -1221,11 +1212,11 @@ class TensorRec(object):
         returns all of them), as plain all-gathers on backends without a device all-to-all (sharding.py).  Euclidean scores:
         every rank certifies its own shard's first k (no floor exchange), then the same merge.
 
-        Which of the routes the call took is kept in ``self.last_route`` (a dict: "route" = cascade_int8 | bf16_filter |
-        euclid_certified | wide_cascade | two_stage | direct | slab (attention models, k > 16 off the wide routes), "k", "sharded",
-        "user_batch_size", "n_items") and, with
-        ``return_route=True``, returned as a third value -- a silently slower route is the likeliest regression of this method
-        (tests/test_gpu_routes.py pins the route of every BASELINE.json configuration).
+        The route is decided by ``topk_plan.plan``, a pure host function (its table: tests/test_topk_plan_host.py).  Which one
+        the call took is kept in ``self.last_route`` (a dict: "route" = cascade_int8 | bf16_filter | euclid_certified |
+        wide_cascade | two_stage | direct | slab (attention models, k > 16 off the wide routes), "k", "sharded", "user_batch_size",
+        "n_items") and, with ``return_route=True``, returned as a third value -- a silently slower route is the likeliest
+        regression of this method (tests/test_gpu_routes.py pins the route of every BASELINE.json configuration).
 
         ``exclude`` (scipy sparse, at most [n_users, n_items]; missing rows / columns exclude nothing): every stored entry != 0
         -- negative interactions included, explicit zeros not -- is left out of that user's list.  The result is the first k
@@ -1280,126 +1271,70 @@ class TensorRec(object):
 
     def _topk_routed(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias, k, batch_size=None, return_device=False,
                      item_sharded=False, item_offset=0, return_route=False, ex=None, drop_self=None, similar=None):
-        """The one routing core of the exact top-k calls (predict_top_k, predict_similar_items_top_k), entered once the
-        representations exist: the route predicates, the item-side operands (prepared once, shared by every batch), the batch loop
-        with its out-of-memory halving, and ``last_route``.  ``query_reprs``: one [n_queries, d] representation per taste (the
-        users of predict_top_k; rows of the item representation for item-item lists); ``attn_reprs``: the attention representations
-        or None; ``query_bias`` / ``item_bias``: projected biases, None for none -- the core never reads ``self.biased``.  ``ex``:
-        predict_top_k's exclusions.  ``drop_self`` (device int32 [n_queries], not together with ``ex``): the id to leave out of
-        each row -- the route is chosen for, and run with, k + 1 places and trec_topk_drop_self reduces the lists to k; the slab
-        route masks its slabs instead.  Runs inside the caller's ``torch.no_grad()`` / variable scope."""
+        """The one core of the exact top-k calls (predict_top_k, predict_similar_items_top_k), entered once the representations
+        exist: gather -> plan -> run.  WHICH route runs is decided by topk_plan.plan from the numbers gathered here (item shards:
+        the all-reduced smallest shard), pinned in tests/test_topk_plan_host.py; this method keeps the collectives, the item-side
+        operands (prepared once, shared by every batch), the batch loops with their out-of-memory halving, and ``last_route``.
+        ``query_reprs``: one [n_queries, d] representation per taste (the users of predict_top_k; rows of the item representation
+        for item-item lists); ``attn_reprs``: the attention representations or None; ``query_bias`` / ``item_bias``: projected
+        biases, None for none -- the core never reads ``self.biased``.  ``ex``: predict_top_k's exclusions.  ``drop_self`` (device
+        int32 [n_queries], not together with ``ex``): the id to leave out of each row -- the route is chosen for, and run with,
+        k + 1 places and trec_topk_drop_self reduces the lists to k; the slab route masks its slabs instead.  Runs inside the
+        caller's ``torch.no_grad()`` / variable scope."""
         from . import sharding
-        graph = self.prediction_graph_factory
+        import torch.distributed as dist
+        graph, group, device = self.prediction_graph_factory, self.process_group, self._store.device
         n_q, n_i = int(query_reprs[0].shape[0]), int(item_repr.shape[0])
-        multi = len(query_reprs) > 1 or attn_reprs is not None
         # the places the routes are chosen for and asked for (exclusions over-fetch per batch, inside the chosen route: fetch_k below)
         k_public, user_batch_size = int(k), batch_size
         if drop_self is not None:
             k = _sim.k_fetch(k_public, True)
-        dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
-        want_sq = graph.engine_mode == ops.MODE_EUCLIDEAN
-        # attention models: the softmax-weighted sum over tastes (recommendation_graphs.py:98-107) does not decompose into
-        # per-taste top-k lists, but it IS independent per (user, item): score slabs of a few thousand users through the
-        # collapse kernel (K9), exact ranks pick the k best of every row -- and item shards merge like any other top-k
-        slab_route = attn_reprs is not None or self.n_components > ops.SCORE_KMAX
-        import torch.distributed as dist
-        sharded = bool(item_sharded) and sharding.active(self.process_group)
-        method, floor_exchange = "auto", None
+        sharded = bool(item_sharded) and sharding.active(group)
+
+        def all_min(value):              # every rank must take the same code path and walk the same batches: the smallest wins
+            t = torch.tensor([value], dtype=torch.int64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
+            return t
+        n_items_min, world, exchanges = n_i, 1, None
         if sharded:
-            # every rank must take the same code path (the floor exchange is a collective): decide on the smallest shard
-            smallest = torch.tensor([n_i], dtype=torch.int64, device=self._store.device)
-            dist.all_reduce(smallest, op=dist.ReduceOp.MIN, group=self.process_group)
-            if int(smallest.item()) >= ops.TWO_STAGE_MIN_ITEMS:
-                method = "two_stage"
+            smallest = all_min(n_i)
+            n_items_min, world = int(smallest.item()), dist.get_world_size(group)
+            floor_fn = None
+            if n_items_min >= ops.TWO_STAGE_MIN_ITEMS:
                 # RCCL: user-partitioned all-to-all (each rank receives 1/world of an all-gather's bytes); else all-gather
-                a2a = sharding.a2a_available(smallest, self.process_group)
-                floor_fn = sharding.shared_topk_floor_a2a if a2a else sharding.shared_topk_floor
-                floor_exchange = lambda sel_max: floor_fn(sel_max, self.process_group)  # noqa: E731
-            else:
-                method = "direct"
-        # precision='fp32' on a large catalogue: the same exact fp32 result, with the contraction done once on bf16 MFMA
-        # as an error-bounded filter and only the survivors re-scored in fp32 (ops.score_topk_filtered)
-        n_items_min = int(smallest.item()) if sharded else n_i
-        filtered = (dtype == ops.DTYPE_F32 and graph.engine_mode == ops.MODE_DOT and 1 <= k <= 16 and
-                    n_items_min >= ops.TWO_STAGE_MIN_ITEMS and self.n_components <= 256 and
-                    ops.N.load().trec_get_tuning(b"topk_bf16_filter", 1) != 0)
-        # Euclidean scores (one taste, fp32): the same cascade finds the 16 NEAREST items of every user -- nearest = largest
-        # u.i - r_i / 2 -- the reference's chain re-scores them and a per-user certificate decides (ops.score_topk_euclid_filtered)
-        # Item shards: every rank certifies ITS shard's first k on its own (the certificate is local: "no other item of this
-        # shard can enter these k places"), the exact per-shard lists merge like any others -- no shared floor, no collective
-        # inside the route, so the ranks need not agree on who falls back.  Several tastes: the same per taste, then the merge
-        # of the taste lists (max over tastes commutes with the monotone bias additions).
-        # 13 <= k <= 48: the same with the 32 / 64 nearest items from the WIDE cascade's lists, where the int8 cascade runs.
-        euclid_wide = (ops.EUCLID_CANDIDATES - 4 < k <= ops.EUCLID_WIDE_K_MAX and
-                       ops.cascade_prefilter_for(self.n_components, n_items_min) == "int8" and ops.i8_user_classes_enabled())
-        euclid_filtered = (dtype == ops.DTYPE_F32 and graph.engine_mode == ops.MODE_EUCLIDEAN and
-                           (1 <= k <= ops.EUCLID_CANDIDATES - 4 or euclid_wide) and n_items_min >= ops.TWO_STAGE_MIN_ITEMS and
-                           self.n_components <= 256 and
-                           ops.N.load().trec_get_tuning(b"topk_euclid_filter", 1) != 0)
-        # 17 <= k <= 64 on a catalogue the cascade runs on: the same int8 -> bf16 stages, 1,024 candidate slots per user and a
-        # wave-per-user finish over every listed item (ops.score_topk_filtered_wide).  Item shards: every rank finds ITS shard's
-        # exact first k on its own (local thresholds, no collective inside the route -- the ranks agree on taking it because the
-        # smallest shard decides), the per-shard lists merge like any others.
-        wide = (dtype == ops.DTYPE_F32 and graph.engine_mode == ops.MODE_DOT and 16 < k <= ops.WIDE_K_MAX and
-                ops.cascade_prefilter_for(self.n_components, n_items_min) == "int8" and
-                ops.N.load().trec_get_tuning(b"topk_bf16_filter", 1) != 0 and ops.i8_user_classes_enabled())
-        # k beyond the 16 entries of the fused lists and off the wide routes (small catalogues, bf16 scores, k > 64 / 48 Euclidean):
-        # exact fp32 score slabs and the k best of every row (ops.topk_from_scores) -- any k, places beyond the catalogue -inf / -1
-        if int(k) > 16 and not wide and not euclid_filtered:
-            slab_route = True
-        stats_exchange = (lambda g: sharding.all_reduce_max(g, self.process_group)) if sharded else None
-        # ... and on a catalogue of >= 262,144 items an int8 MFMA pass (exact integer arithmetic, proven bound) first decides
-        # which (superblock, user) pairs the bf16 stage has to look at at all (csrc/topk_cascade.hip)
-        prefilter = ops.cascade_prefilter_for(self.n_components, n_items_min * (dist.get_world_size(self.process_group) if sharded else 1)) \
-            if filtered else None
-        if slab_route:
-            route_name = "slab"
-        elif euclid_filtered:
-            route_name = "euclid_certified"
-        elif filtered:
-            route_name = "cascade_int8" if prefilter == "int8" else "bf16_filter"
-        elif wide:
-            route_name = "wide_cascade"
-        else:
-            route_name = method if method != "auto" else ("two_stage" if n_i >= ops.TWO_STAGE_MIN_ITEMS else "direct")
+                floor_fn = sharding.shared_topk_floor_a2a if sharding.a2a_available(smallest, group) else sharding.shared_topk_floor
+            exchanges = (floor_fn and (lambda sel_max: floor_fn(sel_max, group)), lambda g: sharding.all_reduce_max(g, group))
+        plan = topk_plan.plan(k, n_i, n_items_min, world, self.n_components, self.precision, graph.engine_mode,
+                              len(query_reprs), attn_reprs is not None)
         # exclusions: the lists are asked for k' places (the same route's largest k at most)
-        k_all = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], 0, n_q))
+        k_all = k if ex is None else _excl.fetch_k(plan.route, k, _excl.max_excluded(ex["indptr"], 0, n_q))
         if user_batch_size is None:
-            route = "wide" if (wide or (euclid_filtered and k > ops.EUCLID_CANDIDATES - 4)) else \
-                ("cascade" if (filtered or euclid_filtered) else "two_stage")
-            user_batch_size = ops.topk_user_batch(n_q, n_i, self.n_components, self._store.device,
-                                                  route=route, k=k_all)
-            if sharded:                  # every rank walks the SAME user batches (each batch holds collectives): the smallest wins
-                ubs = torch.tensor([user_batch_size], dtype=torch.int64, device=self._store.device)
-                dist.all_reduce(ubs, op=dist.ReduceOp.MIN, group=self.process_group)
-                user_batch_size = int(ubs.item())
-        self.last_route = {"route": route_name, "k": k_public, "sharded": bool(sharded), "n_items": n_i,
+            user_batch_size = ops.topk_user_batch(n_q, n_i, self.n_components, device, route=plan.workspace, k=k_all)
+            if sharded:                  # (each batch holds collectives)
+                user_batch_size = int(all_min(user_batch_size).item())
+        self.last_route = {"route": plan.route, "k": k_public, "sharded": bool(sharded), "n_items": n_i,
                            "user_batch_size": int(user_batch_size), "precision": self.precision}
         if ex is not None:
             self.last_route["exclude"] = {"k_fetch": int(k), "n_excluded": ex["n_excluded"], "n_fallback": 0}
         if similar is not None:
             # (the slab route masks the query's own column in its slabs: k places, nothing fetched on top)
-            k = _sim.k_fetch(k_public, drop_self is not None, slab_route)
+            k = _sim.k_fetch(k_public, drop_self is not None, plan.path == "slab")
             self.last_route["similar"] = dict(similar, k_fetch=int(k))
 
         def _ret(v_, i_):
             if ex is not None:
                 self.last_route["exclude"].update(k_fetch=ex["k_fetch"], n_fallback=ex["n_fallback"])
+            if not return_device:
+                v_, i_ = _to_host(v_), _to_host(i_)
             return (v_, i_, dict(self.last_route)) if return_route else (v_, i_)
         vals, idx = [], []
-        if slab_route:
-            # (also: representations wider than the fused kernels' resident operand -- K-looped fp32 GEMM slabs)
-            planes = 1 + (2 * len(query_reprs) if attn_reprs is not None else (len(query_reprs) if multi else 0))
-            step = max(1, min(int(user_batch_size), (1 << 28) // max(1, n_i * planes)))
-            if sharded:                  # (each batch ends in a collective: every rank takes the same steps)
-                st = torch.tensor([step], dtype=torch.int64, device=self._store.device)
-                dist.all_reduce(st, op=dist.ReduceOp.MIN, group=self.process_group)
-                step = int(st.item())
+        if plan.path == "slab":
+            step = topk_plan.slab_step(n_i, len(query_reprs), attn_reprs is not None, user_batch_size)
+            if sharded:                  # (each batch ends in a collective)
+                step = int(all_min(step).item())
             for s in range(0, n_q, step):
                 e = min(s + step, n_q)
-                qb = query_bias[s:e] if query_bias is not None else None
-                attn = [a[s:e] for a in attn_reprs] if attn_reprs is not None else None
-                slab = self._score_slab([q[s:e] for q in query_reprs], attn, item_repr, qb, item_bias)
+                slab = self._score_slab(query_reprs, attn_reprs, item_repr, query_bias, item_bias, rows=slice(s, e))
                 if ex is not None:       # (the slab route needs no over-fetch: its slabs are masked directly)
                     v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"][s:], ex["idx"])
                 elif drop_self is not None:      # (one excluded column per row: the query's own)
@@ -1409,29 +1344,24 @@ class TensorRec(object):
                     v, i = ops.topk_from_scores(slab.contiguous(), k)
                 i = torch.where(i >= 0, i + int(item_offset), i)
                 if sharded:
-                    if sharding.a2a_available(v, self.process_group):
-                        v, i = sharding.sharded_top_k_a2a(v, i, k, self.process_group, replicate=True)
-                    else:
-                        v, i = sharding.sharded_top_k(v, i, k, self.process_group)
+                    v, i = self._merge_shards(v, i, k)
                 vals.append(v)
                 idx.append(i)
-            vals, idx = torch.cat(vals), torch.cat(idx)
-            return _ret(vals, idx) if return_device else _ret(_to_host(vals), _to_host(idx))
+            return _ret(torch.cat(vals), torch.cat(idx))
         ib = item_bias.contiguous() if item_bias is not None else None
-        if filtered or wide:
-            i_f = ops.score_prep_filter(item_repr, normalize=graph.engine_normalize, bias=ib, want_gstats=True)
-        if not filtered and not wide:         # (the wide route works on the filter operand alone)
-            i_op, i_sq, kpad = ops.score_prep(item_repr, dtype, normalize=graph.engine_normalize, want_sqnorm=want_sq)
+        if plan.path in ("filtered", "wide"):         # (the wide route works on the filter operand alone)
+            i_op = ops.score_prep_filter(item_repr, normalize=graph.engine_normalize, bias=ib, want_gstats=True)
+        else:
+            i_op = ops.score_prep(item_repr, ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32,
+                                  normalize=graph.engine_normalize, want_sqnorm=graph.engine_mode == ops.MODE_EUCLIDEAN)
+        items = _TopkItems(item_repr, ib, int(item_offset), i_op)
         s = 0
         while s < n_q:
             e = min(s + user_batch_size, n_q)
             retry = False
-            k_b = k if ex is None else _excl.fetch_k(route_name, k, _excl.max_excluded(ex["indptr"], s, e))
+            k_b = k if ex is None else _excl.fetch_k(plan.route, k, _excl.max_excluded(ex["indptr"], s, e))
             try:
-                v, i = self._topk_user_batch(s, e, query_reprs, item_repr, query_bias, ib, k_b, graph, dtype, want_sq, filtered,
-                                             euclid_filtered, prefilter, sharded, method, floor_exchange, stats_exchange,
-                                             item_offset, i_f if (filtered or wide) else None,
-                                             None if (filtered or wide) else (i_op, i_sq, kpad), wide=wide)
+                v, i = self._topk_user_batch(s, e, k_b, plan, query_reprs, query_bias, items, exchanges)
             except torch.cuda.OutOfMemoryError:
                 # the workspace model of ops.topk_user_batch was too optimistic for this device's state: half the users per
                 # pass (item shards: the ranks walk the same batches and a rank cannot shrink alone -- the error stands)
@@ -1452,11 +1382,8 @@ class TensorRec(object):
             vals.append(v)
             idx.append(i)
             s = e
-        vals, idx = torch.cat(vals), torch.cat(idx)
         self.last_route["user_batch_size"] = int(user_batch_size)          # (after any out-of-memory halving)
-        if return_device:
-            return _ret(vals, idx)
-        return _ret(_to_host(vals), _to_host(idx))
+        return _ret(torch.cat(vals), torch.cat(idx))
 
     # ------------------------------------------------------------------------------------------ candidate sets
     def _candidate_form(self):
@@ -1464,11 +1391,6 @@ class TensorRec(object):
         if self._is_engine_graph() and not self._multi() and self.precision == 'fp32' and self.n_components <= _cand.PAIRS_D_MAX:
             return "pairs"
         return "slab"
-
-    def _candidate_slab_step(self, n_items, n_tastes, attention, user_batch_size):
-        planes = 1 + (2 * n_tastes if attention else (n_tastes if n_tastes > 1 else 0))
-        step = max(1, (1 << 28) // max(1, n_items * planes))
-        return step if user_batch_size is None else max(1, min(step, int(user_batch_size)))
 
     def _candidate_scores(self, form, user_reprs, attn_reprs, item_repr, user_bias, item_bias, indptr, indices, user_batch_size,
                           extra=None):
@@ -1512,14 +1434,7 @@ class TensorRec(object):
                     xs = (p0, p1, xi_d, ops.pair_scores_exact(u_op[s:e], i_op, kpad, d, xu_d, xi_d, ubs_, ibc, graph.engine_mode,
                                                              sq, i_sq))
             else:
-                qb = ub[s:e] if ub is not None else None
-                attn = [a[s:e] for a in attn_reprs] if attn_reprs is not None else None
-                if self._is_engine_graph():
-                    slab = self._score_slab([u[s:e] for u in user_reprs], attn, item_repr, qb, ib)
-                elif self._multi():
-                    slab = self._dense_multi([u[s:e] for u in user_reprs], attn, item_repr, qb, ib)
-                else:
-                    slab = self._dense_prediction(user_reprs[0][s:e], item_repr, qb, ib)
+                slab = self._score_slab(user_reprs, attn_reprs, item_repr, ub, ib, rows=slice(s, e))
                 cu = torch.repeat_interleave(torch.arange(e - s, device=device), (ptr_d[1:] - ptr_d[:-1]))
                 scores = slab[cu, idx_d.long()].to(torch.float32).contiguous()
                 if extra is not None:
@@ -1537,7 +1452,7 @@ class TensorRec(object):
             if form == "pairs":
                 ubs = _cand.default_user_batch(indptr) if user_batch_size is None else max(1, int(user_batch_size))
             else:
-                ubs = self._candidate_slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
+                ubs = topk_plan.slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
             self.last_route = {"route": "candidate_sets", "form": form, "k": int(k), "n_candidates": int(len(indices)),
                                "user_batch_size": int(ubs), "n_items": int(n_items), "sharded": False}
             vals, idx = [], []
@@ -1570,7 +1485,7 @@ class TensorRec(object):
             if form == "pairs":
                 ubs = _cand.default_user_batch(indptr) if user_batch_size is None else max(1, int(user_batch_size))
             else:
-                ubs = self._candidate_slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
+                ubs = topk_plan.slab_step(n_items, len(user_reprs), attn_reprs is not None, user_batch_size)
             rows32 = np.ascontiguousarray(rows, dtype=np.int32)
             for s, e, ptr_d, idx_d, scores, xs in self._candidate_scores(form, user_reprs, attn_reprs, item_repr, user_bias,
                                                                           item_bias, indptr, indices, ubs, extra=(rows32, cols)):
@@ -1582,11 +1497,19 @@ class TensorRec(object):
                 ranks[p0:p1] = (counts + 1).cpu().numpy()
         return ranks
 
-    def _score_slab(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias):
-        """[n_queries, n_items] scores of the slab passes of the top-k core, with the biases it is GIVEN (None: none): one taste is
-        _dense_prediction's engine call; tastes / attention go through _dense_multi, which only predict_top_k reaches."""
+    def _score_slab(self, query_reprs, attn_reprs, item_repr, query_bias, item_bias, rows=None):
+        """[n_queries, n_items] scores by the code ``predict`` runs for this kind of model, with the biases it is GIVEN (None:
+        none): tastes / attention go through _dense_multi (only user-side callers reach it), a user-defined prediction graph through
+        _dense_prediction, one taste of a built-in graph is _dense_prediction's engine call.  ``rows``: a slice or an index tensor
+        of the queries to score (None: all)."""
+        if rows is not None:
+            query_reprs = [q[rows] for q in query_reprs]
+            attn_reprs = [a[rows] for a in attn_reprs] if attn_reprs is not None else None
+            query_bias = query_bias[rows] if query_bias is not None else None
         if len(query_reprs) > 1 or attn_reprs is not None:
             return self._dense_multi(query_reprs, attn_reprs, item_repr, query_bias, item_bias)
+        if not self._is_engine_graph():
+            return self._dense_prediction(query_reprs[0], item_repr, query_bias, item_bias)
         graph = self.prediction_graph_factory
         dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
         qb = query_bias.detach().contiguous() if query_bias is not None else None
@@ -1610,62 +1533,51 @@ class TensorRec(object):
     def _topk_excluded_slabs(self, users, user_reprs, attn_reprs, item_repr, user_bias, item_bias, k, ex):
         """Exact top-k of the given users (device int64 ids) with their excluded items skipped: score slabs of the slab route's
         code (_score_slab, same dtype) and the masked selection of csrc/exclude.hip."""
-        n_i = item_repr.shape[0]
-        n_t = len(user_reprs)
-        planes = 1 + (2 * n_t if attn_reprs is not None else (n_t if n_t > 1 else 0))
-        step = max(1, (1 << 28) // max(1, n_i * planes))
+        step = topk_plan.slab_step(item_repr.shape[0], len(user_reprs), attn_reprs is not None)
         rows32 = users.to(torch.int32)
         vals, idx = [], []
         for s in range(0, users.numel(), step):
-            sel = users[s:s + step]
-            ub = user_bias[sel] if user_bias is not None else None
-            attn = [a[sel] for a in attn_reprs] if attn_reprs is not None else None
-            slab = self._score_slab([u[sel] for u in user_reprs], attn, item_repr, ub, item_bias)
+            slab = self._score_slab(user_reprs, attn_reprs, item_repr, user_bias, item_bias, rows=users[s:s + step])
             v, i = ops.topk_rows_excluded(slab.contiguous(), k, ex["ptr"], ex["idx"], rows=rows32[s:s + step].contiguous())
             vals.append(v)
             idx.append(i)
         return torch.cat(vals), torch.cat(idx)
 
-    def _topk_user_batch(self, s, e, user_reprs, item_repr, user_bias, ib, k, graph, dtype, want_sq, filtered, euclid_filtered,
-                         prefilter, sharded, method, floor_exchange, stats_exchange, item_offset, i_f, i_ops, wide=False):
-        """Users [s, e) of predict_top_k: every taste's exact top-k, merged, and (item shards) exchanged."""
+    def _merge_shards(self, v, i, k):
+        """Per-shard exact lists (global item ids) -> the exact global top-k, the same on every rank."""
         from . import sharding
-        import torch.distributed as dist
+        if sharding.a2a_available(v, self.process_group):
+            return sharding.sharded_top_k_a2a(v, i, k, self.process_group, replicate=True)
+        return sharding.sharded_top_k(v, i, k, self.process_group)
+
+    def _topk_user_batch(self, s, e, k, plan, user_reprs, user_bias, items, exchanges):
+        """Users [s, e) of predict_top_k: every taste's exact top-k by the plan's code path, merged, and (item shards) exchanged.
+        ``items``: the call's _TopkItems; ``exchanges``: (floor_exchange, stats_exchange) on item shards, else None."""
+        graph = self.prediction_graph_factory
         ub = user_bias[s:e].contiguous() if user_bias is not None else None
-        if i_ops is not None:
-            i_op, i_sq, kpad = i_ops
+        floor_exchange, stats_exchange = exchanges if exchanges is not None else (None, None)
         per_taste = []
         for user_repr in user_reprs:
-            if euclid_filtered:
-                per_taste.append(ops.score_topk_euclid_filtered(user_repr[s:e], item_repr, k, ub, ib,
-                                                                item_index_base=int(item_offset)))
-                continue
-            if wide:
+            if plan.path == "euclid":
+                per_taste.append(ops.score_topk_euclid_filtered(user_repr[s:e], items.repr, k, ub, items.bias,
+                                                                item_index_base=items.offset))
+            elif plan.path == "wide":
                 u_f = ops.score_prep_filter(user_repr[s:e], normalize=graph.engine_normalize, sort_users=True, k=k, user_bias=ub)
-                per_taste.append(ops.score_topk_filtered_wide(u_f, i_f, k, ub, ib, item_index_base=int(item_offset)))
-                continue
-            if filtered:
+                per_taste.append(ops.score_topk_filtered_wide(u_f, items.op, k, ub, items.bias, item_index_base=items.offset))
+            elif plan.path == "filtered":
                 u_f = ops.score_prep_filter(user_repr[s:e], normalize=graph.engine_normalize,
-                                            sort_users=prefilter == "int8", k=k, user_bias=ub)
-                # (item shards of >= 4 ranks: a user lists ~27 / world candidates per shard -> four users per wave)
-                lanes = 16 if sharded and dist.get_world_size(self.process_group) >= 4 else 0
-                per_taste.append(ops.score_topk_filtered(u_f, i_f, k, ub, ib, item_index_base=int(item_offset),
-                                                         floor_exchange=floor_exchange,
-                                                         stats_exchange=stats_exchange, prefilter=prefilter,
-                                                         finish_lanes=lanes))
-                continue
-            u_op, u_sq, _ = ops.score_prep(user_repr[s:e], dtype, normalize=graph.engine_normalize,
-                                           want_sqnorm=want_sq)
-            per_taste.append(ops.score_topk(u_op, i_op, dtype, kpad, k, ub, ib, graph.engine_mode, u_sq, i_sq,
-                                            item_index_base=int(item_offset), method=method,
-                                            floor_exchange=floor_exchange))
-        v, i = per_taste[0] if len(per_taste) == 1 else _merge_taste_topk(per_taste, k)
-        if sharded:
-            if sharding.a2a_available(v, self.process_group):
-                v, i = sharding.sharded_top_k_a2a(v, i, k, self.process_group, replicate=True)
+                                            sort_users=plan.prefilter == "int8", k=k, user_bias=ub)
+                per_taste.append(ops.score_topk_filtered(u_f, items.op, k, ub, items.bias, item_index_base=items.offset,
+                                                         floor_exchange=floor_exchange, stats_exchange=stats_exchange,
+                                                         prefilter=plan.prefilter, finish_lanes=plan.finish_lanes))
             else:
-                v, i = sharding.sharded_top_k(v, i, k, self.process_group)
-        return v, i
+                i_op, i_sq, kpad = items.op
+                dtype = ops.DTYPE_BF16 if self.precision == 'bf16' else ops.DTYPE_F32
+                u_op, u_sq, _ = ops.score_prep(user_repr[s:e], dtype, normalize=graph.engine_normalize, want_sqnorm=i_sq is not None)
+                per_taste.append(ops.score_topk(u_op, i_op, dtype, kpad, k, ub, items.bias, graph.engine_mode, u_sq, i_sq,
+                                                item_index_base=items.offset, method=plan.method, floor_exchange=floor_exchange))
+        v, i = per_taste[0] if len(per_taste) == 1 else _merge_taste_topk(per_taste, k)
+        return self._merge_shards(v, i, k) if exchanges is not None else (v, i)
 
     @_on_model_device
     def predict_similar_items(self, item_features, item_ids, n_similar):

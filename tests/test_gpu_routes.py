@@ -106,6 +106,15 @@ def test_k_beyond_the_fused_lists_off_the_wide_route_takes_score_slabs():
         m.predict_top_k(uf, itb, k=0)
 
 
+@pytest.mark.parametrize("graph", [DotProductPredictionGraph, EuclideanSimilarityPredictionGraph])
+def test_wider_than_the_score_kernels_with_k_in_the_wide_range_takes_score_slabs(graph):
+    """n_components > 256 with 17 <= k <= 64 (dot) / 13 <= k <= 48 (Euclidean): the slab route -- the wide routes' int8 question
+    used to be asked first and raised on the width."""
+    nu, ni = 64, 2000
+    uf, itf = sp.identity(nu, dtype=np.float32, format="csr"), sp.identity(ni, dtype=np.float32, format="csr")
+    _check(_model(nu, ni, 300, graph), uf, itf, 20, "slab")
+
+
 @pytest.mark.parametrize("nu,ni,k", [(7, 5, 10), (7, 5, 5), (7, 30, 40), (3, 1, 1)])
 def test_k_at_and_beyond_the_catalogue_size(nu, ni, k):
     """k >= n_items on either kind of route: the first n_items places are the oracle's order, the places beyond hold -inf / -1."""
