@@ -580,6 +580,29 @@ int trec_wmrb_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* p
 int trec_wmrb_bwd(const int64_t* indptr, const int32_t* pos_slot, const float* pos_weight, const float* pred_serial,
                   const float* sample_pred, const float* smr, const float* grad_loss, int64_t n_users,
                   int64_t n_items, int32_t n_sampled, float* d_pred_serial, float* d_sample_pred, void* stream);
+/* Sampled softmax (InfoNCE) and BPR (csrc/loss_sampled.hip).  These replace no TF op chain -- the reference has neither loss --
+ * the formulas are the definition.  Layout and conventions of trec_wmrb_fwd / _bwd: indptr, pos_slot (-1: the interaction
+ * is ignored and its d_pred_serial is 0), pred_serial [n_interactions], sample_pred [n_users, n_sampled], loss [n_positive];
+ * a user without positives writes no loss and gets a zero d_sample_pred row; no atomics, a fixed summation order.
+ * A wave per user for n_sampled <= 256 (tuning wmrb_wave, as for WMRB), a workgroup per user up to 16384.
+ *   sampled softmax, t = inv_temperature (finite, > 0):  loss_p = log(1 + sum_s exp((y_s - y_p) t)), computed as
+ *     M = max_s y_s, Z = sum_s exp((y_s - M) t), m = max(M, y_p), a = exp((y_p - m) t), b = exp((M - m) t), D = a + b Z,
+ *     loss_p = (m - y_p) t + log D;   d y_p = -go_p t b Z / D,   d y_us = t exp((y_us - M) t) sum_{p of u} go_p b_p / D_p.
+ *     row_max, row_sum: [n_users], M and Z, written by the forward pass for the backward pass (users with interactions).
+ *   BPR:  loss_p = (1 / n_sampled) sum_s softplus(y_s - y_p);   d y_p = -(go_p / n_sampled) sum_s sigma(y_s - y_p),
+ *     d y_us = (1 / n_sampled) sum_{p of u} go_p sigma(y_us - y_p).                                                     */
+int trec_sampled_softmax_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial,
+                             const float* sample_pred, int64_t n_users, int32_t n_sampled, float inv_temperature,
+                             float* loss, float* row_max, float* row_sum, void* stream);
+int trec_sampled_softmax_bwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial,
+                             const float* sample_pred, const float* row_max, const float* row_sum,
+                             const float* grad_loss, int64_t n_users, int32_t n_sampled, float inv_temperature,
+                             float* d_pred_serial, float* d_sample_pred, void* stream);
+int trec_bpr_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* sample_pred,
+                 int64_t n_users, int32_t n_sampled, float* loss, void* stream);
+int trec_bpr_bwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* sample_pred,
+                 const float* grad_loss, int64_t n_users, int32_t n_sampled, float* d_pred_serial,
+                 float* d_sample_pred, void* stream);
 /* One WMRB training step's user side in one pass (csrc/wmrb_fused.hip): serial + sample predictions
  * (prediction_graphs.py:52-55 + recommendation_graphs.py:55-57 over tensorrec.py:384-395), the WMRB / BalancedWMRB loss
  * (loss_graphs.py:153-227) and, for the SUM of the loss vector (what tensorrec.py:487-489 minimises), its gradient

@@ -136,6 +136,10 @@ SIGNATURES = {
     "trec_rank_of_pairs_by_user": [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
     "trec_wmrb_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
     "trec_wmrb_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "trec_sampled_softmax_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _f, _vp, _vp, _vp, _vp],
+    "trec_sampled_softmax_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _vp, _vp, _vp],
+    "trec_bpr_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
+    "trec_bpr_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "trec_wmrb_fused_lds_bytes": [_i32, _i32, _i32],
     "trec_wmrb_fused_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp],

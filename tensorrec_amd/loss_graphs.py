@@ -97,3 +97,42 @@ class WMRBLossGraph(AbstractLossGraph):
 class BalancedWMRBLossGraph(WMRBLossGraph):
     """WMRB weighted by value / sum(positive values of the item)  (loss_graphs.py:183-227)."""
     balanced = True
+
+
+class SampledSoftmaxLossGraph(AbstractLossGraph):
+    """
+    Sampled softmax (InfoNCE); not in the reference.  For every POSITIVE interaction p = (u, i), with the user's sampled items s:
+        loss_p = log(1 + sum_s exp((yhat[u, s] - yhat_p) / temperature))
+    i.e. the cross entropy of picking i among {i} + samples.  Magnitudes are ignored, negative interactions are ignored.  A sampled
+    item that happens to be one of the user's positives is kept as a negative: the sampler's contract, the same as for WMRB.
+    Returns the [n_positive_interactions] vector.  The sums factor per user (csrc/loss_sampled.hip): O(S + positives) per user.
+    """
+    is_sample_based = True
+    is_sampled_with_replacement = False
+
+    def __init__(self, temperature=1.0):
+        try:
+            temperature = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+        if not (temperature > 0.0 and temperature != float("inf")):
+            raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+        self.temperature = temperature
+
+    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, **kwargs):
+        return ops.sampled_softmax_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions,
+                                        temperature=self.temperature)
+
+
+class BPRLossGraph(AbstractLossGraph):
+    """
+    Bayesian personalised ranking, the pairwise logistic loss; not in the reference.  For every POSITIVE interaction p = (u, i):
+        loss_p = (1 / S) * sum_s softplus(yhat[u, s] - yhat_p),        softplus(x) = log(1 + exp(x))
+    Magnitudes are ignored, negative interactions are ignored.  A sampled item that happens to be one of the user's positives is
+    kept as a negative: the sampler's contract, the same as for WMRB.  Returns the [n_positive_interactions] vector.
+    """
+    is_sample_based = True
+    is_sampled_with_replacement = False
+
+    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, **kwargs):
+        return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions)

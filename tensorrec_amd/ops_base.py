@@ -745,6 +745,57 @@ class _WMRB(torch.autograd.Function):
         return dp, ds, None, None
 
 
+class _SampledSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_serial, sample_pred, inter: Interactions, inv_temperature):
+        pred_serial, sample_pred = _f32c(pred_serial), _f32c(sample_pred)
+        n_users = inter.shape[0]
+        S = sample_pred.shape[1]
+        loss = torch.empty((inter.n_positive,), dtype=torch.float32, device=pred_serial.device)
+        row_max = torch.empty((n_users,), dtype=torch.float32, device=pred_serial.device)
+        row_sum = torch.empty_like(row_max)
+        N.call("trec_sampled_softmax_fwd", N.ptr(inter.indptr), N.ptr(inter.pos_slot), N.ptr(pred_serial), N.ptr(sample_pred),
+               n_users, S, inv_temperature, N.ptr(loss), N.ptr(row_max), N.ptr(row_sum))
+        ctx.inter, ctx.inv_temperature = inter, inv_temperature
+        ctx.save_for_backward(pred_serial, sample_pred, row_max, row_sum)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        pred_serial, sample_pred, row_max, row_sum = ctx.saved_tensors
+        inter = ctx.inter
+        S = sample_pred.shape[1]
+        dp = torch.empty_like(pred_serial)
+        ds = torch.empty_like(sample_pred)
+        N.call("trec_sampled_softmax_bwd", N.ptr(inter.indptr), N.ptr(inter.pos_slot), N.ptr(pred_serial), N.ptr(sample_pred),
+               N.ptr(row_max), N.ptr(row_sum), N.ptr(_f32c(gl)), inter.shape[0], S, ctx.inv_temperature, N.ptr(dp), N.ptr(ds))
+        return dp, ds, None, None
+
+
+class _BPR(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_serial, sample_pred, inter: Interactions):
+        pred_serial, sample_pred = _f32c(pred_serial), _f32c(sample_pred)
+        S = sample_pred.shape[1]
+        loss = torch.empty((inter.n_positive,), dtype=torch.float32, device=pred_serial.device)
+        N.call("trec_bpr_fwd", N.ptr(inter.indptr), N.ptr(inter.pos_slot), N.ptr(pred_serial), N.ptr(sample_pred), inter.shape[0], S,
+               N.ptr(loss))
+        ctx.inter = inter
+        ctx.save_for_backward(pred_serial, sample_pred)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        pred_serial, sample_pred = ctx.saved_tensors
+        inter = ctx.inter
+        S = sample_pred.shape[1]
+        dp = torch.empty_like(pred_serial)
+        ds = torch.empty_like(sample_pred)
+        N.call("trec_bpr_bwd", N.ptr(inter.indptr), N.ptr(inter.pos_slot), N.ptr(pred_serial), N.ptr(sample_pred), N.ptr(_f32c(gl)),
+               inter.shape[0], S, N.ptr(dp), N.ptr(ds))
+        return dp, ds, None
+
+
 import os as _os
 
 # sampled pairs from which the rank-free binned grouping replaces histogram atomics + ranked fill (TREC_BINNED_MIN_PAIRS: A/B runs)
@@ -977,6 +1028,24 @@ def wmrb_loss(pred_serial, sample_pred, interactions, balanced=False):
         raise ValueError("tf_sample_predictions must have one row per user")
     weight = interactions.balanced_weight() if balanced else None
     return _WMRB.apply(pred_serial, sample_pred, interactions, weight)
+
+
+def sampled_softmax_loss(pred_serial, sample_pred, interactions, temperature=1.0):
+    """[n_positive] vector log(1 + sum_s exp((y_us - y_p) / temperature)) (csrc/loss_sampled.hip); non-positive interactions are
+    ignored, a sampled item that is one of the user's positives stays a negative"""
+    if sample_pred.shape[0] != interactions.shape[0]:
+        raise ValueError("tf_sample_predictions must have one row per user")
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+    return _SampledSoftmax.apply(pred_serial, sample_pred, interactions, 1.0 / temperature)
+
+
+def bpr_loss(pred_serial, sample_pred, interactions):
+    """[n_positive] vector mean_s softplus(y_us - y_p) (csrc/loss_sampled.hip); conventions of sampled_softmax_loss"""
+    if sample_pred.shape[0] != interactions.shape[0]:
+        raise ValueError("tf_sample_predictions must have one row per user")
+    return _BPR.apply(pred_serial, sample_pred, interactions)
 
 
 class _RMSE(torch.autograd.Function):

@@ -37,7 +37,8 @@ from .errors import (
 )
 from .framework import VariableStore, variable_scope, resolve_device
 from .loss_graphs import (AbstractLossGraph, RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph,
-                          BalancedWMRBLossGraph, SeparationLossGraph, SeparationDenseLossGraph)
+                          BalancedWMRBLossGraph, SeparationLossGraph, SeparationDenseLossGraph, SampledSoftmaxLossGraph,
+                          BPRLossGraph)
 from .prediction_graphs import AbstractPredictionGraph, DotProductPredictionGraph
 from .recommendation_graphs import (
     project_biases, bias_prediction_dense, bias_prediction_serial, rank_predictions,
@@ -1813,7 +1814,7 @@ class TensorRec(object):
 # (every built-in loss is made of this library's launches only: the separation losses lost their boolean-mask host syncs when
 # they became streaming reductions, csrc/loss_dense.hip)
 _GRAPH_CAPTURABLE_LOSSES = (RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph, BalancedWMRBLossGraph, SeparationLossGraph,
-                            SeparationDenseLossGraph)
+                            SeparationDenseLossGraph, SampledSoftmaxLossGraph, BPRLossGraph)
 MAX_GRAPHED_BATCHES = 64        # graphs kept alive by one fit call; further batches run eagerly
 
 
