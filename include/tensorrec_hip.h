@@ -603,6 +603,36 @@ int trec_bpr_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* pr
 int trec_bpr_bwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* sample_pred,
                  const float* grad_loss, int64_t n_users, int32_t n_sampled, float* d_pred_serial,
                  float* d_sample_pred, void* stream);
+/* The same two losses with accidental hits removed and / or the logQ correction (csrc/loss_sampled.hip, docs/sampled_losses.md).
+ * x_item: the CSR's int32 column ids, sorted within a row (a row holds a column once); samples: int32 [n_users, n_sampled], the
+ * item ids behind sample_pred.  A sample is a HIT when its item is the column of an interaction of the same user with
+ * pos_slot >= 0; with remove_hits a hit leaves every sum and its d_sample_pred is an exact 0 (the mask is per user).
+ *   sampled softmax:  loss_p = log(1 + sum_{s kept} exp((y_s - y_p) t + c_s)),  c_s = -log(n_sampled q(item_s)) with
+ *     log_q_correction, else 0;  log q from log_q [n_items], or, when log_q is NULL, the scalar log_q_uniform for every item; an
+ *     id outside [0, n_items) gets c = 0.  Computed as R = max_kept y_s, w_s = (y_s - R) t + c_s, M = max_kept w_s,
+ *     Z = sum_kept exp(w_s - M), w_p = (y_p - R) t, m = max(M, w_p), D = exp(w_p - m) + exp(M - m) Z, loss_p = (m - w_p) + log D;
+ *     row_ref, row_max, row_sum: [n_users], R, M and Z for the backward pass, which recomputes the mask and c.  A user whose
+ *     samples are all hits: loss_p = 0, d y_p = 0, a zero d_sample_pred row.
+ *   BPR:  loss_p = (1 / n_sampled) sum_{s kept} softplus(y_s - y_p) -- still divided by n_sampled; no logQ term, no log_q argument.
+ * Checks as above; also TREC_ERR_INVALID for null samples with an option on, null x_item with remove_hits, n_items outside
+ * [1, 2^31) with log_q_correction.  With both options off the pair computes the plain loss (in the R / w form above).            */
+int trec_sampled_softmax_adj_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                                 const float* pred_serial, const float* sample_pred, const int32_t* samples, const float* log_q,
+                                 float log_q_uniform, int64_t n_users, int64_t n_items, int32_t n_sampled, float inv_temperature,
+                                 int32_t log_q_correction, int32_t remove_hits, float* loss, float* row_ref, float* row_max,
+                                 float* row_sum, void* stream);
+int trec_sampled_softmax_adj_bwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                                 const float* pred_serial, const float* sample_pred, const int32_t* samples, const float* log_q,
+                                 float log_q_uniform, const float* row_ref, const float* row_max, const float* row_sum,
+                                 const float* grad_loss, int64_t n_users, int64_t n_items, int32_t n_sampled,
+                                 float inv_temperature, int32_t log_q_correction, int32_t remove_hits, float* d_pred_serial,
+                                 float* d_sample_pred, void* stream);
+int trec_bpr_adj_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
+                     const float* sample_pred, const int32_t* samples, int64_t n_users, int32_t n_sampled, int32_t remove_hits,
+                     float* loss, void* stream);
+int trec_bpr_adj_bwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
+                     const float* sample_pred, const int32_t* samples, const float* grad_loss, int64_t n_users, int32_t n_sampled,
+                     int32_t remove_hits, float* d_pred_serial, float* d_sample_pred, void* stream);
 /* One WMRB training step's user side in one pass (csrc/wmrb_fused.hip): serial + sample predictions
  * (prediction_graphs.py:52-55 + recommendation_graphs.py:55-57 over tensorrec.py:384-395), the WMRB / BalancedWMRB loss
  * (loss_graphs.py:153-227) and, for the SUM of the loss vector (what tensorrec.py:487-489 minimises), its gradient
@@ -706,6 +736,14 @@ int trec_rmse_bwd(const float* y, const float* pred, const float* loss, const fl
  * stream of GLOBAL user user_base + r, so user shards reproduce the whole-population draw.                      */
 int trec_sample_items(int64_t n_users, int64_t user_base, int32_t n_items, int32_t n_sampled, int32_t replace,
                       uint64_t seed, uint32_t step, int32_t* out, void* stream);
+/* Popularity-weighted sampling WITH replacement from a Walker alias table (csrc/sampler_alias.hip; no counterpart in the
+ * reference): thr uint32 [n_items], alias int32 [n_items] with entries in [0, n_items).  Sample s of global user u takes the
+ * words (w0, w1) = words (0, 1) (s even) or (2, 3) (s odd) of Philox4x32-10(counter (u_lo, s >> 1, step, 0x414C4953 + u_hi), seed):
+ * j = (w0 * n_items) >> 32, out = w1 < thr[j] ? j : alias[j] -- strictly below, so thr 0 never accepts and a column of
+ * probability 1 carries 2^32 - 1 with alias[j] = j.  q_i n_items 2^32 = thr[i] + sum_{j: alias[j] = i} (2^32 - thr[j]) exactly.
+ * TREC_ERR_INVALID for a null pointer, n_items < 1, n_sampled < 1; n_users == 0 is a no-op.                              */
+int trec_sample_items_alias(int64_t n_users, int64_t user_base, int32_t n_items, int32_t n_sampled, const uint32_t* thr,
+                            const int32_t* alias, uint64_t seed, uint32_t step, int32_t* out, void* stream);
 
 /* ---- K8: optimiser --------------------------------------------------------------------------------------------
  * tf.train.AdamOptimizer(lr).minimize (tensorrec.py:489) + gradient of alpha * sum(tf.nn.l2_loss(w)) (:487-488):

@@ -140,6 +140,11 @@ SIGNATURES = {
     "trec_sampled_softmax_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _vp, _vp, _vp],
     "trec_bpr_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
     "trec_bpr_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "trec_sampled_softmax_adj_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, _i64, _i32, _f, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "trec_sampled_softmax_adj_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f, _i32, _i32,
+                                     _vp, _vp, _vp],
+    "trec_bpr_adj_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
+    "trec_bpr_adj_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "trec_wmrb_fused_lds_bytes": [_i32, _i32, _i32],
     "trec_wmrb_fused_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp],
@@ -159,6 +164,7 @@ SIGNATURES = {
     "trec_rmse_fwd": [_vp, _vp, _i64, _vp, _i32, _vp, _vp],
     "trec_rmse_bwd": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_sample_items": [_i64, _i64, _i32, _i32, _i32, _u64, _u32, _vp, _vp],
+    "trec_sample_items_alias": [_i64, _i64, _i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp],
     "trec_crc32c": [_vp, _u64, _u32],
     "trec_collapse_tastes_fwd": [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_collapse_tastes_bwd": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],

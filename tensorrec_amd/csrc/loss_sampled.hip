@@ -83,6 +83,94 @@ __device__ __forceinline__ float sigmoid_f(float x)
     return (x >= 0.f ? 1.0f : e) / (1.0f + e);
 }
 
+// ---- the adjusted forms: accidental hits and the logQ correction ---------------------------------------------------------------
+// A sample of user u is a HIT when its item is the column of one of the user's interactions with pos_slot >= 0 (a value <= 0 is no
+// hit).  A row holds a column once and sorted (sparse.Interactions), so the thread that owns the sample does one binary search over
+// x_item[b..e) and checks pos_slot of the match: once per sample per kernel, shared by all the user's positives.  A hit becomes
+// padding (-inf): it never wins a maximum, adds exp(-inf) = 0 / softplus(-inf) = 0 / sigma(-inf) = 0, and its gradient is an exact 0.
+// The correction of a kept sample is c = -(log S + log q(item)), log q from the [n_items] table or the scalar of the uniform case;
+// an id outside [0, n_items) is not looked up (c = 0).  Both are recomputed by the backward pass: nothing of size [U, S] is stored.
+#define SL_ADJ_LOGQ 1
+#define SL_ADJ_HITS 2
+
+struct SlAdj {
+    const int32_t* x_item;      // CSR column ids (int32, sorted within a row); needed for SL_ADJ_HITS
+    const int32_t* samples;     // [n_users, S] sampled item ids; needed when a flag is set
+    const float* log_q;         // [n_items] log q, or NULL: log_q_uniform for every item
+    float log_q_uniform;
+    float log_s;                // log S
+    int32_t n_items;
+    int32_t flags;
+};
+
+__device__ __forceinline__ bool sl_is_hit(const int32_t* __restrict__ x_item, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e,
+                                          int32_t item)
+{
+    int64_t lo = b, hi = e;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (x_item[mid] < item) lo = mid + 1; else hi = mid;
+    }
+    return lo < e && x_item[lo] == item && pos_slot[lo] >= 0;
+}
+
+// prediction y of the sample at flat position `at` of user row [b, e): -inf when it is a hit, else y with its correction in c
+__device__ __forceinline__ float sl_adjust(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e, int64_t at,
+                                           float y, float& c)
+{
+    c = 0.f;
+    if (adj.flags == 0) return y;
+    const int32_t item = adj.samples[at];
+    if ((adj.flags & SL_ADJ_HITS) && sl_is_hit(adj.x_item, pos_slot, b, e, item)) return -INFINITY;
+    if ((adj.flags & SL_ADJ_LOGQ) && (uint32_t)item < (uint32_t)adj.n_items)
+        c = -(adj.log_s + (adj.log_q ? adj.log_q[item] : adj.log_q_uniform));
+    return y;
+}
+
+// The wave-per-user forms keep a row of at most 64 interactions in registers -- lane i holds column i (INT32_MAX beyond the row) and
+// whether it is a positive -- and search it with lane shuffles instead of memory loads: a branchless lower bound, six steps.  Every
+// lane of the wave calls sl_adjust_wave (a lane without a sample passes live = false and gets its -inf padding back); longer rows
+// take the binary search in memory.  The conditions on adj.flags and row.whole are wave-uniform.
+struct SlRow { int32_t col; int32_t pos; bool whole; };
+
+__device__ __forceinline__ SlRow sl_row_wave(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e, int lane)
+{
+    SlRow row;
+    row.whole = e - b <= 64;
+    row.col = 0x7fffffff;
+    row.pos = 0;
+    if ((adj.flags & SL_ADJ_HITS) && row.whole && b + lane < e) {
+        row.col = adj.x_item[b + lane];
+        row.pos = pos_slot[b + lane] >= 0;
+    }
+    return row;
+}
+
+__device__ __forceinline__ float sl_adjust_wave(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e,
+                                                const SlRow& row, bool live, int64_t at, float y, float& c)
+{
+    c = 0.f;
+    if (adj.flags == 0) return y;
+    const int32_t item = live ? adj.samples[at] : -1;
+    if (adj.flags & SL_ADJ_HITS) {
+        bool hit;
+        if (row.whole) {
+            int at_row = 0;                                         // columns [0, at_row) are below the item
+#pragma unroll
+            for (int step = 32; step > 0; step >>= 1)
+                if (__shfl(row.col, at_row + step - 1, 64) < item) at_row += step;
+            const int32_t col = __shfl(row.col, at_row, 64), is_pos = __shfl(row.pos, at_row, 64);
+            hit = col == item && is_pos != 0;
+        } else {
+            hit = live && sl_is_hit(adj.x_item, pos_slot, b, e, item);
+        }
+        if (hit) return -INFINITY;
+    }
+    if (live && (adj.flags & SL_ADJ_LOGQ) && (uint32_t)item < (uint32_t)adj.n_items)
+        c = -(adj.log_s + (adj.log_q ? adj.log_q[item] : adj.log_q_uniform));
+    return y;
+}
+
 // ---- sampled softmax: wave per user (S <= 256) ----------------------------------------------------------------
 // Samples sit in <= 4 registers per lane (sample s = r * 64 + lane), padded with -inf: the padding never wins the maximum
 // (S >= 1) and adds exp(-inf) = 0 to Z.  The positives are taken 64 per pass, one per lane: O(1) work each.
@@ -219,159 +307,210 @@ __global__ __launch_bounds__(256) void ssm_bwd_kernel(
         d_samp[u * S + s] = any ? (t * expf((samp[u * S + s] - M) * t)) * K : 0.f;
 }
 
-// ---- BPR: wave per user (S <= 256) --------------------------------------------------------------------------------
-// The loop structure of wmrb_*_wave_kernel: 64 positives loaded per pass and broadcast.  The -inf padding gives x = -inf:
-// softplus = max(-inf, 0) + log1p(exp(-inf)) = 0 and sigma = exp(-inf) / (1 + exp(-inf)) = 0, so a padded lane adds nothing.
-// Every cell costs an expf and a log1pf or a division, so registers that hold padding only (S = 100: two of the four) are skipped.
-__global__ __launch_bounds__(256) void bpr_fwd_wave_kernel(
+// ---- adjusted sampled softmax --------------------------------------------------------------------------------------------
+//     loss_p = log(1 + sum_{s kept} exp((y_s - y_p) t + c_s)),   kept: not a hit;   c_s as in sl_adjust (0 without the correction)
+//     per user          R = max_{kept} y_s;   w_s = (y_s - R) t + c_s;   M = max_{kept} w_s;   Z = sum_{kept} exp(w_s - M)  (>= 1)
+//     per positive      w_p = (y_p - R) t;  the terms of ssm_terms on (w_p, M, Z) with t = 1:   loss_p = (m - w_p) + log D
+//     backward          d y_p = -go_p t b Z / D,   d y_us = t exp(w_s - M) K_u for a kept sample, an exact 0 for a hit
+// Only the negatives carry c.  R keeps every argument a difference of predictions as in the plain kernels (scores far from 0 lose
+// nothing); M is the maximum of the corrected logits, so no exponential overflows.  (R, M, Z) are stored per user for the backward
+// pass, which recomputes the mask and c.  A user whose samples are all hits has R = -inf: loss_p = 0, d y_p = 0, a zero d_samp row.
+__global__ __launch_bounds__(256) void ssm_adj_fwd_wave_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
-    const float* __restrict__ samp, int64_t n_users, int32_t S, float inv_s, float* __restrict__ loss)
+    const float* __restrict__ samp, int64_t n_users, int32_t S, float t, float* __restrict__ loss, float* __restrict__ Ru,
+    float* __restrict__ Mu, float* __restrict__ Zu, SlAdj adj)
 {
     const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     if (u >= n_users) return;
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    float ys[SL_WAVE_SR];
-#pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
-    for (int64_t p0 = b; p0 < e; p0 += 64) {
-        const int np = (int)((e - p0 < 64) ? (e - p0) : 64);
-        int32_t slot = -1;
-        float yp = 0.f;
-        if (lane < np) {
-            slot = pos_slot[p0 + lane];
-            yp = pred[p0 + lane];
-        }
-        float mine = 0.f;
-        for (int q = 0; q < np; ++q) {
-            if (__shfl(slot, q, 64) < 0) continue;                 // wave-uniform
-            const float ypq = __shfl(yp, q, 64);
-            float acc = 0.f;
-#pragma unroll
-            for (int r = 0; r < SL_WAVE_SR; ++r)
-                if (r * 64 < S) acc += softplus_f(ys[r] - ypq);    // (wave-uniform: a register of padding only costs nothing)
-            acc = wave_sum(acc);
-            if (lane == q) mine = acc * inv_s;
-        }
-        if (lane < np && slot >= 0) loss[slot] = mine;
-    }
-}
-
-__global__ __launch_bounds__(256) void bpr_bwd_wave_kernel(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
-    const float* __restrict__ samp, const float* __restrict__ grad_out, int64_t n_users, int32_t S, float inv_s,
-    float* __restrict__ d_pred, float* __restrict__ d_samp)
-{
-    const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (u >= n_users) return;
-    const int lane = lane_id();
-    const int64_t b = indptr[u], e = indptr[u + 1];
-    float ys[SL_WAVE_SR], acc[SL_WAVE_SR];
+    const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+    float ys[SL_WAVE_SR], cs[SL_WAVE_SR];
 #pragma unroll
     for (int r = 0; r < SL_WAVE_SR; ++r) {
-        ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
-        acc[r] = 0.f;
+        const bool live = r * 64 + lane < S;
+        ys[r] = sl_adjust_wave(adj, pos_slot, b, e, row, live, u * S + r * 64 + lane, live ? samp[u * S + r * 64 + lane] : -INFINITY, cs[r]);
     }
-    for (int64_t p0 = b; p0 < e; p0 += 64) {
-        const int np = (int)((e - p0 < 64) ? (e - p0) : 64);
-        float c = 0.f, yp = 0.f;
-        if (lane < np) {
-            const int32_t slot = pos_slot[p0 + lane];
-            yp = pred[p0 + lane];
-            if (slot >= 0) c = grad_out[slot] * inv_s;
-        }
-        float my_dp = 0.f;
-        for (int q = 0; q < np; ++q) {
-            const float cq = __shfl(c, q, 64);
-            if (cq == 0.f) continue;                               // wave-uniform; d_pred stays 0
-            const float ypq = __shfl(yp, q, 64);
-            float sg = 0.f;
+    float R = fmaxf(fmaxf(ys[0], ys[1]), fmaxf(ys[2], ys[3]));
+    for (int off = 32; off > 0; off >>= 1) R = fmaxf(R, __shfl_xor(R, off, 64));
+    const bool none = R == -INFINITY;                              // wave-uniform: every sample is a hit
+    float M = 0.f, Z = 0.f;
+    if (!none) {
+        float w[SL_WAVE_SR];
 #pragma unroll
-            for (int r = 0; r < SL_WAVE_SR; ++r) {
-                if (r * 64 >= S) continue;                         // (wave-uniform: a register of padding only costs nothing)
-                const float sig = sigmoid_f(ys[r] - ypq);
-                sg += sig;
-                acc[r] += cq * sig;
-            }
-            sg = wave_sum(sg);
-            if (lane == q) my_dp = -cq * sg;
-        }
-        if (lane < np) d_pred[p0 + lane] = my_dp;
+        for (int r = 0; r < SL_WAVE_SR; ++r) w[r] = (ys[r] - R) * t + cs[r];      // -inf for a hit or padding
+        M = fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
+        for (int off = 32; off > 0; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, 64));
+        float z = 0.f;
+#pragma unroll
+        for (int r = 0; r < SL_WAVE_SR; ++r) z += expf(w[r] - M);
+        Z = wave_sum(z);
     }
-#pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r)
-        if (r * 64 + lane < S) d_samp[u * S + r * 64 + lane] = acc[r];
+    if (lane == 0) { Ru[u] = R; Mu[u] = M; Zu[u] = Z; }
+    for (int64_t p = b + lane; p < e; p += 64) {
+        const int32_t slot = pos_slot[p];
+        if (slot < 0) continue;
+        float lo = 0.f;
+        if (!none) {
+            const float wp = (pred[p] - R) * t;
+            float m, bb, bz, D;
+            ssm_terms(wp, M, Z, 1.0f, m, bb, bz, D);
+            lo = (m - wp) + logf(D);
+        }
+        loss[slot] = lo;
+    }
 }
 
-// ---- BPR: workgroup per user (S <= 16384) ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bpr_fwd_kernel(
+__global__ __launch_bounds__(256) void ssm_adj_bwd_wave_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
-    const float* __restrict__ samp, int32_t S, float inv_s, float* __restrict__ loss)
+    const float* __restrict__ samp, const float* __restrict__ Ru, const float* __restrict__ Mu, const float* __restrict__ Zu,
+    const float* __restrict__ grad_out, int64_t n_users, int32_t S, float t, float* __restrict__ d_pred,
+    float* __restrict__ d_samp, SlAdj adj)
 {
-    extern __shared__ float lds[];           // [S] sampled predictions of this user
+    const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (u >= n_users) return;
+    const int lane = lane_id();
+    const int64_t b = indptr[u], e = indptr[u + 1];
+    float K = 0.f, M = 0.f, R = 0.f;
+    bool any = false;                                              // wave-uniform: a positive and a kept sample
+    if (b != e) {
+        R = Ru[u];
+        M = Mu[u];
+        const float Z = Zu[u];
+        const bool none = R == -INFINITY;
+        for (int64_t p0 = b; p0 < e; p0 += 64) {
+            const int np = (int)((e - p0 < 64) ? (e - p0) : 64);
+            float term = 0.f;
+            bool is_pos = false;
+            if (lane < np) {
+                const int32_t slot = pos_slot[p0 + lane];
+                float dp = 0.f;
+                if (slot >= 0 && !none) {
+                    const float go = grad_out[slot];
+                    float m, bb, bz, D;
+                    ssm_terms((pred[p0 + lane] - R) * t, M, Z, 1.0f, m, bb, bz, D);
+                    dp = -(go * t) * (bz / D);
+                    term = (go * bb) / D;
+                    is_pos = true;
+                }
+                d_pred[p0 + lane] = dp;
+            }
+            any = any || (__builtin_amdgcn_ballot_w64(is_pos) != 0ull);
+            for (int q = 0; q < np; ++q) K += __shfl(term, q, 64); // interaction order; a non-positive adds an exact 0
+        }
+    }
+    const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+#pragma unroll
+    for (int r = 0; r < SL_WAVE_SR; ++r) {
+        const int s = r * 64 + lane;
+        if (r * 64 >= S) continue;                                 // (wave-uniform)
+        float d = 0.f;
+        if (any) {                                                 // (wave-uniform: every lane takes part in the row search)
+            float c;
+            const float y = sl_adjust_wave(adj, pos_slot, b, e, row, s < S, u * S + s, s < S ? samp[u * S + s] : -INFINITY, c);
+            if (y != -INFINITY) d = (t * expf(((y - R) * t + c) - M)) * K;
+        }
+        if (s < S) d_samp[u * S + s] = d;
+    }
+}
+
+// workgroup per user: LDS holds the samples' (masked) predictions, then their corrected logits w in place, and the corrections
+__global__ __launch_bounds__(256) void ssm_adj_fwd_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
+    const float* __restrict__ samp, int32_t S, float t, float* __restrict__ loss, float* __restrict__ Ru, float* __restrict__ Mu,
+    float* __restrict__ Zu, SlAdj adj)
+{
+    extern __shared__ float lds[];           // [S] y, then w | [S] c
+    __shared__ float red[256];
+    float* l_w = lds;
+    float* l_c = lds + S;
     const int64_t u = blockIdx.x;
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    fill_samples(lds, samp, u, S);
-    __syncthreads();
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    for (int64_t p = b + wave; p < e; p += 4) {
+    float mx = -INFINITY;
+    for (int s = threadIdx.x; s < S; s += 256) {                   // (a thread reads back only the slots it wrote)
+        float c;
+        const float y = sl_adjust(adj, pos_slot, b, e, u * S + s, samp[u * S + s], c);
+        l_w[s] = y;
+        l_c[s] = c;
+        mx = fmaxf(mx, y);
+    }
+    const float R = wg_max(mx, red);
+    const bool none = R == -INFINITY;
+    float M = 0.f, Z = 0.f;
+    if (!none) {
+        mx = -INFINITY;
+        for (int s = threadIdx.x; s < S; s += 256) {
+            const float w = (l_w[s] - R) * t + l_c[s];
+            l_w[s] = w;
+            mx = fmaxf(mx, w);
+        }
+        M = wg_max(mx, red);
+        float z = 0.f;
+        for (int s = threadIdx.x; s < S; s += 256) z += expf(l_w[s] - M);
+        Z = wg_sum(z, red);
+    }
+    if (threadIdx.x == 0) { Ru[u] = R; Mu[u] = M; Zu[u] = Z; }
+    for (int64_t p = b + threadIdx.x; p < e; p += 256) {
         const int32_t slot = pos_slot[p];
         if (slot < 0) continue;
-        const float yp = pred[p];
-        float acc = 0.f;
-        for (int s = lane; s < S; s += 64) acc += softplus_f(lds[s] - yp);
-        acc = wave_sum(acc);
-        if (lane == 0) loss[slot] = acc * inv_s;
+        float lo = 0.f;
+        if (!none) {
+            const float wp = (pred[p] - R) * t;
+            float m, bb, bz, D;
+            ssm_terms(wp, M, Z, 1.0f, m, bb, bz, D);
+            lo = (m - wp) + logf(D);
+        }
+        loss[slot] = lo;
     }
 }
 
-__global__ __launch_bounds__(256) void bpr_bwd_kernel(
+__global__ __launch_bounds__(256) void ssm_adj_bwd_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
-    const float* __restrict__ samp, const float* __restrict__ grad_out, int32_t S, float inv_s,
-    float* __restrict__ d_pred, float* __restrict__ d_samp)
+    const float* __restrict__ samp, const float* __restrict__ Ru, const float* __restrict__ Mu, const float* __restrict__ Zu,
+    const float* __restrict__ grad_out, int32_t S, float t, float* __restrict__ d_pred, float* __restrict__ d_samp, SlAdj adj)
 {
-    extern __shared__ float lds[];           // [S] samples | [SL_MAX_POS_LDS] yp | [SL_MAX_POS_LDS] c
-    float* l_s = lds;
-    float* l_yp = lds + S;
-    float* l_c = l_yp + SL_MAX_POS_LDS;
+    __shared__ float red[256];
     const int64_t u = blockIdx.x;
     const int64_t b = indptr[u], e = indptr[u + 1];
-    fill_samples(l_s, samp, u, S);
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    for (int64_t p0 = b; p0 < e || p0 == b; p0 += SL_MAX_POS_LDS) {
-        const int np = (int)((e - p0 < SL_MAX_POS_LDS) ? (e - p0) : SL_MAX_POS_LDS);
-        __syncthreads();
-        for (int q = threadIdx.x; q < np; q += 256) {
-            const int32_t slot = pos_slot[p0 + q];
-            l_yp[q] = pred[p0 + q];
-            l_c[q] = slot >= 0 ? grad_out[slot] * inv_s : 0.f;
+    float R = -INFINITY, M = 0.f, Z = 1.f, k = 0.f, n_pos = 0.f;
+    if (b != e) { R = Ru[u]; M = Mu[u]; Z = Zu[u]; }
+    const bool none = R == -INFINITY;
+    for (int64_t p = b + threadIdx.x; p < e; p += 256) {
+        const int32_t slot = pos_slot[p];
+        float dp = 0.f;
+        if (slot >= 0 && !none) {
+            const float go = grad_out[slot];
+            float m, bb, bz, D;
+            ssm_terms((pred[p] - R) * t, M, Z, 1.0f, m, bb, bz, D);
+            dp = -(go * t) * (bz / D);
+            k += (go * bb) / D;
+            n_pos += 1.f;
         }
-        __syncthreads();
-        // (1) gradient w.r.t. the positive's own prediction: waves over positives, lanes over samples
-        for (int q = wave; q < np; q += 4) {
-            const float c = l_c[q];
-            if (c == 0.f) { if (lane == 0) d_pred[p0 + q] = 0.f; continue; }
-            const float yp = l_yp[q];
-            float sg = 0.f;
-            for (int s = lane; s < S; s += 64) sg += sigmoid_f(l_s[s] - yp);
-            sg = wave_sum(sg);
-            if (lane == 0) d_pred[p0 + q] = -c * sg;
+        d_pred[p] = dp;
+    }
+    const float K = wg_sum(k, red);
+    const bool any = wg_max(n_pos, red) > 0.f;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        float d = 0.f;
+        if (any) {
+            float c;
+            const float y = sl_adjust(adj, pos_slot, b, e, u * S + s, samp[u * S + s], c);
+            if (y != -INFINITY) d = (t * expf(((y - R) * t + c) - M)) * K;
         }
-        // (2) gradient w.r.t. the shared samples: threads own s, loop over this pass's positives in order
-        for (int s = threadIdx.x; s < S; s += 256) {
-            const float ys = l_s[s];
-            float acc = (p0 == b) ? 0.f : d_samp[u * S + s];
-            for (int q = 0; q < np; ++q) {
-                const float c = l_c[q];
-                if (c != 0.f) acc += c * sigmoid_f(ys - l_yp[q]);   // (uniform over the workgroup)
-            }
-            d_samp[u * S + s] = acc;
-        }
-        if (e == b) break;
+        d_samp[u * S + s] = d;
     }
 }
+
+// ---- BPR ---------------------------------------------------------------------------------------------------------------
+// The kernels live in loss_sampled_bpr_body.hpp and are compiled twice: the plain ones, and the ones that drop accidental hits.
+#define SL_ADJ 0
+#include "loss_sampled_bpr_body.hpp"
+#undef SL_ADJ
+#define SL_ADJ 1
+#include "loss_sampled_bpr_body.hpp"
+#undef SL_ADJ
 
 // ---- entry points ------------------------------------------------------------------------------------------------
 // dynamic LDS above 64 KB (S close to 16384) has to be asked for
@@ -469,4 +608,124 @@ extern "C" int trec_bpr_bwd(const int64_t* indptr, const int32_t* pos_slot, cons
     hipLaunchKernelGGL(bpr_bwd_kernel, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream, indptr, pos_slot, pred_serial,
                        sample_pred, grad_loss, n_sampled, inv_s, d_pred_serial, d_sample_pred);
     return trec_check_launch("trec_bpr_bwd");
+}
+
+// ---- entry points of the adjusted forms ---------------------------------------------------------------------------------
+static inline SlAdj make_adj(const int32_t* x_item, const int32_t* samples, const float* log_q, float log_q_uniform, int64_t n_items,
+                             int32_t n_sampled, int32_t log_q_correction, int32_t remove_hits)
+{
+    SlAdj adj;
+    adj.x_item = x_item;
+    adj.samples = samples;
+    adj.log_q = log_q;
+    adj.log_q_uniform = log_q_uniform;
+    adj.log_s = (float)log((double)n_sampled);
+    adj.n_items = (int32_t)n_items;
+    adj.flags = (log_q_correction ? SL_ADJ_LOGQ : 0) | (remove_hits ? SL_ADJ_HITS : 0);
+    return adj;
+}
+
+#define SL_ADJ_REQUIRE(name)                                                                                                            \
+    TREC_REQUIRE(n_sampled >= 1 && n_sampled <= 16384, name ": n_sampled must be in [1, 16384]");                                       \
+    TREC_REQUIRE(!(log_q_correction || remove_hits) || samples, name ": null samples with an option that needs them");                  \
+    TREC_REQUIRE(!remove_hits || x_item, name ": null x_item with remove_hits");                                                        \
+    TREC_REQUIRE(!log_q_correction || (n_items >= 1 && n_items <= 2147483647), name ": n_items must be in [1, 2^31) with log_q_correction")
+
+extern "C" int trec_sampled_softmax_adj_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                                            const float* pred_serial, const float* sample_pred, const int32_t* samples,
+                                            const float* log_q, float log_q_uniform, int64_t n_users, int64_t n_items,
+                                            int32_t n_sampled, float inv_temperature, int32_t log_q_correction, int32_t remove_hits,
+                                            float* loss, float* row_ref, float* row_max, float* row_sum, void* stream)
+{
+    TREC_REQUIRE(indptr && pos_slot && pred_serial && sample_pred && loss && row_ref && row_max && row_sum,
+                 "trec_sampled_softmax_adj_fwd: null pointer");
+    SL_ADJ_REQUIRE("trec_sampled_softmax_adj_fwd");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_sampled_softmax_adj_fwd: inv_temperature must be finite and > 0");
+    if (n_users == 0) return TREC_OK;
+    const SlAdj adj = make_adj(x_item, samples, log_q, log_q_uniform, n_items, n_sampled, log_q_correction, remove_hits);
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(ssm_adj_fwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_temperature, loss, row_ref, row_max,
+                           row_sum, adj);
+        return trec_check_launch("trec_sampled_softmax_adj_fwd");
+    }
+    const size_t lds = sizeof(float) * 2 * (size_t)n_sampled;
+    allow_lds(ssm_adj_fwd_kernel, lds + 1024);
+    hipLaunchKernelGGL(ssm_adj_fwd_kernel, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream, indptr, pos_slot, pred_serial,
+                       sample_pred, n_sampled, inv_temperature, loss, row_ref, row_max, row_sum, adj);
+    return trec_check_launch("trec_sampled_softmax_adj_fwd");
+}
+
+extern "C" int trec_sampled_softmax_adj_bwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                                            const float* pred_serial, const float* sample_pred, const int32_t* samples,
+                                            const float* log_q, float log_q_uniform, const float* row_ref, const float* row_max,
+                                            const float* row_sum, const float* grad_loss, int64_t n_users, int64_t n_items,
+                                            int32_t n_sampled, float inv_temperature, int32_t log_q_correction, int32_t remove_hits,
+                                            float* d_pred_serial, float* d_sample_pred, void* stream)
+{
+    TREC_REQUIRE(indptr && pos_slot && pred_serial && sample_pred && row_ref && row_max && row_sum && grad_loss && d_pred_serial &&
+                     d_sample_pred,
+                 "trec_sampled_softmax_adj_bwd: null pointer");
+    SL_ADJ_REQUIRE("trec_sampled_softmax_adj_bwd");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_sampled_softmax_adj_bwd: inv_temperature must be finite and > 0");
+    if (n_users == 0) return TREC_OK;
+    const SlAdj adj = make_adj(x_item, samples, log_q, log_q_uniform, n_items, n_sampled, log_q_correction, remove_hits);
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(ssm_adj_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           indptr, pos_slot, pred_serial, sample_pred, row_ref, row_max, row_sum, grad_loss, n_users, n_sampled,
+                           inv_temperature, d_pred_serial, d_sample_pred, adj);
+        return trec_check_launch("trec_sampled_softmax_adj_bwd");
+    }
+    hipLaunchKernelGGL(ssm_adj_bwd_kernel, dim3((unsigned)n_users), dim3(256), 0, (hipStream_t)stream, indptr, pos_slot, pred_serial,
+                       sample_pred, row_ref, row_max, row_sum, grad_loss, n_sampled, inv_temperature, d_pred_serial, d_sample_pred, adj);
+    return trec_check_launch("trec_sampled_softmax_adj_bwd");
+}
+
+// BPR has no logQ term: the adjusted pair takes the ids for the hit test only
+extern "C" int trec_bpr_adj_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
+                                const float* sample_pred, const int32_t* samples, int64_t n_users, int32_t n_sampled,
+                                int32_t remove_hits, float* loss, void* stream)
+{
+    const int32_t log_q_correction = 0;
+    const int64_t n_items = 0;
+    TREC_REQUIRE(indptr && pos_slot && pred_serial && sample_pred && loss, "trec_bpr_adj_fwd: null pointer");
+    SL_ADJ_REQUIRE("trec_bpr_adj_fwd");
+    if (n_users == 0) return TREC_OK;
+    const SlAdj adj = make_adj(x_item, samples, nullptr, 0.f, n_items, n_sampled, 0, remove_hits);
+    const float inv_s = 1.0f / (float)n_sampled;
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(bpr_fwd_wave_adj_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_s, loss, adj);
+        return trec_check_launch("trec_bpr_adj_fwd");
+    }
+    const size_t lds = sizeof(float) * (size_t)n_sampled;
+    allow_lds(bpr_fwd_adj_kernel, lds);
+    hipLaunchKernelGGL(bpr_fwd_adj_kernel, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream, indptr, pos_slot, pred_serial,
+                       sample_pred, n_sampled, inv_s, loss, adj);
+    return trec_check_launch("trec_bpr_adj_fwd");
+}
+
+extern "C" int trec_bpr_adj_bwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
+                                const float* sample_pred, const int32_t* samples, const float* grad_loss, int64_t n_users,
+                                int32_t n_sampled, int32_t remove_hits, float* d_pred_serial, float* d_sample_pred, void* stream)
+{
+    const int32_t log_q_correction = 0;
+    const int64_t n_items = 0;
+    TREC_REQUIRE(indptr && pos_slot && pred_serial && sample_pred && grad_loss && d_pred_serial && d_sample_pred,
+                 "trec_bpr_adj_bwd: null pointer");
+    SL_ADJ_REQUIRE("trec_bpr_adj_bwd");
+    if (n_users == 0) return TREC_OK;
+    const SlAdj adj = make_adj(x_item, samples, nullptr, 0.f, n_items, n_sampled, 0, remove_hits);
+    const float inv_s = 1.0f / (float)n_sampled;
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(bpr_bwd_wave_adj_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           indptr, pos_slot, pred_serial, sample_pred, grad_loss, n_users, n_sampled, inv_s, d_pred_serial,
+                           d_sample_pred, adj);
+        return trec_check_launch("trec_bpr_adj_bwd");
+    }
+    const size_t lds = sizeof(float) * ((size_t)n_sampled + 2 * SL_MAX_POS_LDS);
+    allow_lds(bpr_bwd_adj_kernel, lds);
+    hipLaunchKernelGGL(bpr_bwd_adj_kernel, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream, indptr, pos_slot, pred_serial,
+                       sample_pred, grad_loss, n_sampled, inv_s, d_pred_serial, d_sample_pred, adj);
+    return trec_check_launch("trec_bpr_adj_bwd");
 }

@@ -11,6 +11,12 @@ import abc
 from . import ops
 
 
+def _as_bool(name, value):
+    if not isinstance(value, bool) and type(value).__name__ != "bool_":        # (bool or numpy.bool_)
+        raise ValueError("%s must be a bool, got %r" % (name, value))
+    return bool(value)
+
+
 class AbstractLossGraph(object):
     __metaclass__ = abc.ABCMeta
 
@@ -21,6 +27,8 @@ class AbstractLossGraph(object):
     is_sample_based = False
     # If True, and if is_sample_based is True, predictions will be sampled with replacement
     is_sampled_with_replacement = False
+    # If True, and if is_sample_based is True, the sampled item ids and their log-probabilities will be passed to the loss function
+    wants_sample_items = False
 
     @abc.abstractmethod
     def connect_loss_graph(self, tf_prediction_serial, tf_interactions_serial, tf_interactions, tf_n_users, tf_n_items,
@@ -30,6 +38,10 @@ class AbstractLossGraph(object):
         tf_interactions (sparse.Interactions: .indices, .values, .dense_shape), tf_n_users, tf_n_items.
         If is_dense: tf_prediction [n_users, n_items], tf_rankings [n_users, n_items].
         If is_sample_based: tf_sample_predictions [n_users, n_sampled_items], tf_n_sampled_items.
+        If is_sample_based and wants_sample_items (a class or instance attribute, default False): tf_sample_items, the int32
+        [n_users, n_sampled_items] item ids behind tf_sample_predictions, and tf_sample_log_q, a float32 [n_items] tensor of the
+        sampler's log-probabilities (``sampler.log_q(device)``) or None when the sampler has no such method, which means uniform.
+        A graph that leaves the flag False receives exactly the kwargs above.
         :return: the loss value (scalar or vector tensor).
         """
         pass
@@ -106,11 +118,22 @@ class SampledSoftmaxLossGraph(AbstractLossGraph):
     i.e. the cross entropy of picking i among {i} + samples.  Magnitudes are ignored, negative interactions are ignored.  A sampled
     item that happens to be one of the user's positives is kept as a negative: the sampler's contract, the same as for WMRB.
     Returns the [n_positive_interactions] vector.  The sums factor per user (csrc/loss_sampled.hip): O(S + positives) per user.
+
+    ``remove_accidental_hits=True``: a sample that IS one of the user's positive interactions of the batch leaves the sum (the mask is
+    per user, shared by the user's positives).  ``log_q_correction=True``: every kept sample's logit gets -log(S q(item)), q the
+    sampler's probability (``sampler.log_q``; a sampler without that method is taken as uniform): the importance-sampling estimate of
+    the full softmax's partition function for S independent draws -- meant for samplers that draw WITH replacement (PopularitySampler).
+    With both off (the default) a step is the plain loss's, bit for bit.  docs/sampled_losses.md.
     """
     is_sample_based = True
     is_sampled_with_replacement = False
 
-    def __init__(self, temperature=1.0):
+    log_q_correction = remove_accidental_hits = False            # (models pickled before the options existed)
+
+    def __init__(self, temperature=1.0, log_q_correction=False, remove_accidental_hits=False):
+        self.log_q_correction = _as_bool("log_q_correction", log_q_correction)
+        self.remove_accidental_hits = _as_bool("remove_accidental_hits", remove_accidental_hits)
+        self.wants_sample_items = self.log_q_correction or self.remove_accidental_hits
         try:
             temperature = float(temperature)
         except (TypeError, ValueError):
@@ -119,9 +142,15 @@ class SampledSoftmaxLossGraph(AbstractLossGraph):
             raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
         self.temperature = temperature
 
-    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, **kwargs):
+    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, tf_sample_items=None,
+                           tf_sample_log_q=None, **kwargs):
+        if not self.wants_sample_items:
+            return ops.sampled_softmax_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions,
+                                            temperature=self.temperature)
         return ops.sampled_softmax_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions,
-                                        temperature=self.temperature)
+                                        temperature=self.temperature, sample_items=tf_sample_items, sample_log_q=tf_sample_log_q,
+                                        log_q_correction=self.log_q_correction,
+                                        remove_accidental_hits=self.remove_accidental_hits)
 
 
 class BPRLossGraph(AbstractLossGraph):
@@ -130,9 +159,19 @@ class BPRLossGraph(AbstractLossGraph):
         loss_p = (1 / S) * sum_s softplus(yhat[u, s] - yhat_p),        softplus(x) = log(1 + exp(x))
     Magnitudes are ignored, negative interactions are ignored.  A sampled item that happens to be one of the user's positives is
     kept as a negative: the sampler's contract, the same as for WMRB.  Returns the [n_positive_interactions] vector.
+    ``remove_accidental_hits=True`` drops those samples from the sum, which is still divided by S.  There is no logQ term.
     """
     is_sample_based = True
     is_sampled_with_replacement = False
 
-    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, **kwargs):
-        return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions)
+    remove_accidental_hits = False                               # (models pickled before the option existed)
+
+    def __init__(self, remove_accidental_hits=False):
+        self.remove_accidental_hits = _as_bool("remove_accidental_hits", remove_accidental_hits)
+        self.wants_sample_items = self.remove_accidental_hits
+
+    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, tf_sample_items=None, **kwargs):
+        if not self.remove_accidental_hits:
+            return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions)
+        return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions, sample_items=tf_sample_items,
+                            remove_accidental_hits=True)

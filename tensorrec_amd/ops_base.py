@@ -6,6 +6,8 @@ libtensorrec_hip.so (tensorrec_amd/_native.py); the public module is tensorrec_a
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _native as N
@@ -796,6 +798,66 @@ class _BPR(torch.autograd.Function):
         return dp, ds, None
 
 
+class _SampledSoftmaxAdjusted(torch.autograd.Function):
+    """trec_sampled_softmax_adj_fwd / _bwd: hits removed and / or the logQ correction; ``adj`` = (sample_items, log_q or None,
+    log_q_uniform, log_q_correction, remove_hits)"""
+
+    @staticmethod
+    def forward(ctx, pred_serial, sample_pred, inter: Interactions, inv_temperature, adj):
+        pred_serial, sample_pred = _f32c(pred_serial), _f32c(sample_pred)
+        items, log_q, lq_uniform, use_q, no_hits = adj
+        n_users, n_items = inter.shape
+        S = sample_pred.shape[1]
+        loss = torch.empty((inter.n_positive,), dtype=torch.float32, device=pred_serial.device)
+        rows = torch.empty((3, n_users), dtype=torch.float32, device=pred_serial.device)
+        N.call("trec_sampled_softmax_adj_fwd", N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot), N.ptr(pred_serial),
+               N.ptr(sample_pred), N.ptr(items), N.ptr(log_q), lq_uniform, n_users, n_items, S, inv_temperature, use_q, no_hits,
+               N.ptr(loss), N.ptr(rows[0]), N.ptr(rows[1]), N.ptr(rows[2]))
+        ctx.inter, ctx.inv_temperature, ctx.adj = inter, inv_temperature, adj
+        ctx.save_for_backward(pred_serial, sample_pred, rows)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        pred_serial, sample_pred, rows = ctx.saved_tensors
+        inter = ctx.inter
+        items, log_q, lq_uniform, use_q, no_hits = ctx.adj
+        n_users, n_items = inter.shape
+        S = sample_pred.shape[1]
+        dp = torch.empty_like(pred_serial)
+        ds = torch.empty_like(sample_pred)
+        N.call("trec_sampled_softmax_adj_bwd", N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot), N.ptr(pred_serial),
+               N.ptr(sample_pred), N.ptr(items), N.ptr(log_q), lq_uniform, N.ptr(rows[0]), N.ptr(rows[1]), N.ptr(rows[2]),
+               N.ptr(_f32c(gl)), n_users, n_items, S, ctx.inv_temperature, use_q, no_hits, N.ptr(dp), N.ptr(ds))
+        return dp, ds, None, None, None
+
+
+class _BPRAdjusted(torch.autograd.Function):
+    """trec_bpr_adj_fwd / _bwd: accidental hits removed"""
+
+    @staticmethod
+    def forward(ctx, pred_serial, sample_pred, inter: Interactions, items):
+        pred_serial, sample_pred = _f32c(pred_serial), _f32c(sample_pred)
+        S = sample_pred.shape[1]
+        loss = torch.empty((inter.n_positive,), dtype=torch.float32, device=pred_serial.device)
+        N.call("trec_bpr_adj_fwd", N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot), N.ptr(pred_serial),
+               N.ptr(sample_pred), N.ptr(items), inter.shape[0], S, 1, N.ptr(loss))
+        ctx.inter, ctx.items = inter, items
+        ctx.save_for_backward(pred_serial, sample_pred)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        pred_serial, sample_pred = ctx.saved_tensors
+        inter = ctx.inter
+        S = sample_pred.shape[1]
+        dp = torch.empty_like(pred_serial)
+        ds = torch.empty_like(sample_pred)
+        N.call("trec_bpr_adj_bwd", N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot), N.ptr(pred_serial),
+               N.ptr(sample_pred), N.ptr(ctx.items), N.ptr(_f32c(gl)), inter.shape[0], S, 1, N.ptr(dp), N.ptr(ds))
+        return dp, ds, None, None
+
+
 import os as _os
 
 # sampled pairs from which the rank-free binned grouping replaces histogram atomics + ranked fill (TREC_BINNED_MIN_PAIRS: A/B runs)
@@ -1030,22 +1092,54 @@ def wmrb_loss(pred_serial, sample_pred, interactions, balanced=False):
     return _WMRB.apply(pred_serial, sample_pred, interactions, weight)
 
 
-def sampled_softmax_loss(pred_serial, sample_pred, interactions, temperature=1.0):
+def _checked_sample_items(sample_items, sample_pred):
+    """the int32 [n_users, S] id table behind ``sample_pred``, for the options that need it"""
+    if sample_items is None:
+        raise ValueError("log_q_correction / remove_accidental_hits need sample_items, the [n_users, n_sampled] ids of the samples")
+    if tuple(sample_items.shape) != tuple(sample_pred.shape):
+        raise ValueError("sample_items has shape %s, the sample predictions %s" % (tuple(sample_items.shape), tuple(sample_pred.shape)))
+    return sample_items.to(torch.int32).contiguous()
+
+
+def sampled_softmax_loss(pred_serial, sample_pred, interactions, temperature=1.0, sample_items=None, sample_log_q=None,
+                         log_q_correction=False, remove_accidental_hits=False):
     """[n_positive] vector log(1 + sum_s exp((y_us - y_p) / temperature)) (csrc/loss_sampled.hip); non-positive interactions are
-    ignored, a sampled item that is one of the user's positives stays a negative"""
+    ignored, a sampled item that is one of the user's positives stays a negative.
+
+    ``remove_accidental_hits``: a sample whose item (``sample_items`` int32 [n_users, S]) is one of the user's positive interactions
+    of this batch leaves the sum.  ``log_q_correction``: every kept sample's logit gets -log(S q(item)), ``sample_log_q`` float32
+    [n_items] holding log q (None: uniform, q = 1 / n_items); the correction is the one for S independent draws.  With both off
+    the call is the plain one: the same autograd Function and launches."""
     if sample_pred.shape[0] != interactions.shape[0]:
         raise ValueError("tf_sample_predictions must have one row per user")
     temperature = float(temperature)
     if not (temperature > 0.0 and temperature != float("inf")):
         raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
-    return _SampledSoftmax.apply(pred_serial, sample_pred, interactions, 1.0 / temperature)
+    if not (log_q_correction or remove_accidental_hits):
+        return _SampledSoftmax.apply(pred_serial, sample_pred, interactions, 1.0 / temperature)
+    items = _checked_sample_items(sample_items, sample_pred)
+    n_items = interactions.shape[1]
+    log_q = None
+    if log_q_correction and sample_log_q is not None:
+        if sample_log_q.numel() != n_items:
+            raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
+        log_q = _f32c(sample_log_q).reshape(-1)
+    adj = (items, log_q, -math.log(n_items), 1 if log_q_correction else 0, 1 if remove_accidental_hits else 0)
+    return _SampledSoftmaxAdjusted.apply(pred_serial, sample_pred, interactions, 1.0 / temperature, adj)
 
 
-def bpr_loss(pred_serial, sample_pred, interactions):
-    """[n_positive] vector mean_s softplus(y_us - y_p) (csrc/loss_sampled.hip); conventions of sampled_softmax_loss"""
+def bpr_loss(pred_serial, sample_pred, interactions, sample_items=None, sample_log_q=None, log_q_correction=False,
+             remove_accidental_hits=False):
+    """[n_positive] vector mean_s softplus(y_us - y_p) (csrc/loss_sampled.hip); conventions of sampled_softmax_loss.
+    ``remove_accidental_hits`` as there, the sum still divided by S.  BPR has no logQ term: ``log_q_correction`` must stay False
+    (``sample_log_q`` is accepted and ignored, so both losses take the same keywords)."""
     if sample_pred.shape[0] != interactions.shape[0]:
         raise ValueError("tf_sample_predictions must have one row per user")
-    return _BPR.apply(pred_serial, sample_pred, interactions)
+    if log_q_correction:
+        raise ValueError("BPR has no logQ term: log_q_correction is not available for bpr_loss")
+    if not remove_accidental_hits:
+        return _BPR.apply(pred_serial, sample_pred, interactions)
+    return _BPRAdjusted.apply(pred_serial, sample_pred, interactions, _checked_sample_items(sample_items, sample_pred))
 
 
 class _RMSE(torch.autograd.Function):
@@ -1326,6 +1420,20 @@ def sample_items(n_users, n_items, n_sampled, replace, seed, step, device="cuda"
     out = torch.empty((n_users, n_sampled), dtype=torch.int32, device=device)
     with _timed("sample_items"):
         N.call("trec_sample_items", n_users, int(user_base), n_items, n_sampled, 1 if replace else 0,
+               int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, N.ptr(out))
+    return out
+
+
+def sample_items_alias(n_users, n_items, n_sampled, thr, alias, seed, step, device="cuda", user_base=0):
+    """int32 [n_users, n_sampled] drawn with replacement from the alias table (thr: uint32 bits in an int32 tensor [n_items], alias
+    int32 [n_items]); csrc/sampler_alias.hip"""
+    if thr.numel() != n_items or alias.numel() != n_items:
+        raise ValueError("the alias table has %d / %d entries, expected n_items = %d" % (thr.numel(), alias.numel(), n_items))
+    out = torch.empty((n_users, n_sampled), dtype=torch.int32, device=device)
+    if n_users == 0:                    # (an empty tensor has no address to hand over)
+        return out
+    with _timed("sample_items_alias"):
+        N.call("trec_sample_items_alias", n_users, int(user_base), n_items, n_sampled, N.ptr(thr), N.ptr(alias),
                int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, N.ptr(out))
     return out
 

@@ -65,6 +65,108 @@ class DeviceSampler(object):
         return ops.sample_items(n_users, n_items, n_sampled_items, replace, self.seed, step, device, user_base)
 
 
+ALIAS_ONE = (1 << 32) - 1       # threshold of an alias column of probability 1 (the kernel accepts w < thr)
+
+
+def build_alias_table(weights):
+    """Walker's alias table of ``weights`` (float64, non-negative, not all zero) with integer thresholds: (thr uint32 [n], alias
+    int32 [n]).  Column j keeps item j for a word w < thr[j] and gives alias[j] otherwise (csrc/sampler_alias.hip).  Built in float64
+    and deterministically: the small (p < 1) and large (p >= 1) columns are two stacks filled in index order, popped from the end.
+    A column of probability 1, and whatever rounding leaves on either stack, gets ALIAS_ONE and its own index as alias."""
+    w = np.asarray(weights, dtype=np.float64)
+    n = w.size
+    p = w * (n / w.sum())
+    prob = np.ones(n, np.float64)
+    alias = np.arange(n, dtype=np.int64)
+    small = [int(i) for i in np.flatnonzero(p < 1.0)]
+    large = [int(i) for i in np.flatnonzero(p >= 1.0)]
+    p = p.tolist()
+    while small and large:
+        s, g = small.pop(), large.pop()
+        prob[s], alias[s] = p[s], g
+        p[g] = (p[g] + p[s]) - 1.0
+        (small if p[g] < 1.0 else large).append(g)
+    thr = np.minimum(np.floor(prob * 4294967296.0 + 0.5), float(ALIAS_ONE))
+    thr[alias == np.arange(n)] = float(ALIAS_ONE)
+    return thr.astype(np.uint32), alias.astype(np.int32)
+
+
+def alias_table_counts(thr, alias):
+    """q_i * n * 2^32 as exact integers (uint64 [n]): thr[i] + sum over the columns j with alias[j] = i of (2^32 - thr[j])"""
+    num = thr.astype(np.uint64)
+    np.add.at(num, alias.astype(np.int64), np.uint64(1 << 32) - thr.astype(np.uint64))
+    return num
+
+
+class PopularitySampler(object):
+    """K7a: negatives drawn from q_i proportional to (count_i + smoothing) ** power with Walker's alias method on the GPU
+    (csrc/sampler_alias.hip).  ``item_counts``: a length-n_items array of non-negative counts, or a scipy sparse interactions matrix
+    (then: per item, the number of entries with a value > 0).  ``power=0`` is uniform; an item of weight 0 is never drawn.
+
+    ALWAYS draws with replacement and ignores ``replace``: weighted sampling without replacement is not offered, and the
+    -log(S q) correction of SampledSoftmaxLossGraph(log_q_correction=True) is the one for S independent draws.  Row r of a table is
+    the stream of the global user user_base + r, so user shards draw what the whole population would; the streams differ from
+    DeviceSampler's under the same seed.
+
+    The table (uint32 thresholds, int32 aliases) is built once on the host and uploaded once per device.  ``log_q(device)`` is
+    log q_i of the distribution the TABLE implements -- exact integers over n_items * 2^32, logarithm in float64, stored as float32,
+    -inf for an item that is never drawn -- which is what the loss corrects with."""
+
+    def __init__(self, item_counts, power=0.75, smoothing=0.0, seed=0):
+        import scipy.sparse as sp
+        if sp.issparse(item_counts):
+            m = sp.coo_matrix(item_counts)
+            counts = np.bincount(m.col[m.data > 0], minlength=m.shape[1]).astype(np.float64)
+        else:
+            counts = np.asarray(item_counts, dtype=np.float64).reshape(-1)
+        power, smoothing = float(power), float(smoothing)
+        if counts.size < 1 or not np.isfinite(counts).all() or (counts < 0).any():
+            raise ValueError("item_counts must be a non-empty vector of finite, non-negative counts")
+        if not (power >= 0.0 and np.isfinite(power)):
+            raise ValueError("power must be a finite float >= 0, got %r" % (power,))
+        if not (smoothing >= 0.0 and np.isfinite(smoothing)):
+            raise ValueError("smoothing must be a finite float >= 0, got %r" % (smoothing,))
+        base = counts + smoothing
+        weights = np.power(base, power)                     # (0 ** 0 = 1: power 0 is uniform over every item)
+        if not np.isfinite(weights).all() or not (weights.sum() > 0):
+            raise ValueError("the weights (count + smoothing) ** power are all zero (or overflow)")
+        self.seed, self.power, self.smoothing = int(seed), power, smoothing
+        self.n_items = int(counts.size)
+        self.thr, self.alias = build_alias_table(weights)
+        self._device = {}
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_device"] = {}             # device copies are rebuilt on demand (save_model pickles the model object)
+        return state
+
+    def probabilities(self):
+        """float64 [n_items]: the distribution the table implements, exactly"""
+        return alias_table_counts(self.thr, self.alias).astype(np.float64) / (float(self.n_items) * 4294967296.0)
+
+    def _on(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = str(device)
+        if key not in self._device:
+            num = alias_table_counts(self.thr, self.alias).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                log_q = np.log(num) - np.log(float(self.n_items) * 4294967296.0)
+            self._device[key] = (torch.from_numpy(self.thr.view(np.int32)).to(device), torch.from_numpy(self.alias).to(device),
+                                 torch.from_numpy(log_q.astype(np.float32)).to(device))
+        return self._device[key]
+
+    def log_q(self, device):
+        return self._on(device)[2]
+
+    def sample(self, n_items, n_users, n_sampled_items, replace, step, device, user_base=0):
+        if int(n_items) != self.n_items:
+            raise ValueError("PopularitySampler was built for %d items, asked to sample from %d" % (self.n_items, n_items))
+        thr, alias, _ = self._on(device)
+        return ops.sample_items_alias(n_users, self.n_items, int(n_sampled_items), thr, alias, self.seed, step, device, user_base)
+
+
 class HostSampler(object):
     """The reference's sampler verbatim in behaviour (util.sample_items on the host, util.py:12-21), uploaded each
     step.  ``rng`` is anything with ``.choice`` (default: the global ``np.random`` as in the reference)."""
@@ -773,6 +875,12 @@ class TensorRec(object):
                     'tf_sample_predictions': densify_sampled_item_predictions(samp_serial, n_sampled_items, n_users),
                     'tf_n_sampled_items': n_sampled_items,
                 })
+                if getattr(loss_graph, 'wants_sample_items', False):
+                    log_q = getattr(self.sampler, 'log_q', None)
+                    loss_kwargs.update({
+                        'tf_sample_items': samples,
+                        'tf_sample_log_q': log_q(self._store.device) if callable(log_q) else None,
+                    })
 
             # (user shards: a scalar loss is ONE number over the union batch -- its sums cross the ranks inside the loss op)
             with ops.scalar_loss_group(self.process_group, active=self._dp_active()):
