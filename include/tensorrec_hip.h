@@ -653,6 +653,25 @@ int trec_wmrb_fused_step(const float* U, const float* V, const float* user_bias,
                          int32_t max_interactions_per_user, float* loss, float* pred_serial, float* dU,
                          float* d_user_bias, float* coef_samples, float* coef_pairs, int32_t* sample_hist,
                          int32_t* sample_rank, void* stream);
+/* One training step's user side of the SAMPLED SOFTMAX loss in one pass (csrc/softmax_fused.hip): the arguments, the outputs
+ * and the coverage of trec_wmrb_fused_step -- gather, dU and the rank epilogue are the same code (csrc/user_fused_body.hpp) --
+ * without pos_weight and with the loss of trec_sampled_softmax_fwd / _bwd, or of trec_sampled_softmax_adj_fwd / _bwd when a
+ * flag is set, at upstream gradient 1.  inv_temperature: finite, > 0.  log_q_correction != 0: every kept sample's logit gets
+ * -(log n_sampled + log q(item)), log q from log_q [n_items] or, with log_q NULL, log_uniform = -log(n_items); n_items must
+ * lie in [1, 2^31).  remove_hits != 0: a sample whose item is the column of one of the user's interactions with
+ * pos_slot >= 0 leaves the sums and gets a coefficient of exactly 0 (tested against the user's interaction ids on chip); a
+ * user whose samples are all hits gets loss 0 and zero coefficients.  Errors before any launch: TREC_ERR_INVALID for null
+ * pointers, a bad inv_temperature, user_bias without d_user_bias or the reverse, sample_rank without sample_hist, n_items
+ * out of range with the correction, null interaction arrays with remove_hits; TREC_ERR_UNSUPPORTED for a shape
+ * trec_softmax_fused_lds_bytes answers with -1 (then run the generic step). */
+int trec_softmax_fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d);
+int trec_softmax_fused_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
+                            const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const int32_t* samples,
+                            int64_t n_users, int64_t n_items, int32_t n_sampled, int32_t d,
+                            int32_t max_interactions_per_user, float inv_temperature, const float* log_q, float log_uniform,
+                            int32_t log_q_correction, int32_t remove_hits, float* loss, float* pred_serial, float* dU,
+                            float* d_user_bias, float* coef_samples, float* coef_pairs, int32_t* sample_hist,
+                            int32_t* sample_rank, void* stream);
 /* The same step for S in the thousands, long interaction rows and Euclidean scores (csrc/wmrb_tiled.hip): the user's S + n_u item
  * rows are streamed twice in tiles (scores into LDS, then the coefficient-weighted sum dU) instead of living in registers.
  * mode 0: dot scores (prediction_graphs.py:52-55; cosine = dot on normalised rows, :70-72); mode 1: euclidean,

@@ -873,6 +873,78 @@ def wmrb_fused_supported(n_sampled, interactions, d):
     return N.query("trec_wmrb_fused_lds_bytes", int(n_sampled), int(interactions.max_row_nnz), int(d)) >= 0
 
 
+def _fused_sample_grouping(xs, n_users, n_items, S, dev):
+    """How the item side of a one-pass fused step groups the sampled pairs: (binned_bytes, ws32, ranks).  Very many sampled pairs: grouped
+    by item through a two-level LDS partition that needs no ranks (csrc/segment.hip, "binned") -- the fused kernel then issues no
+    histogram atomics at all (ws32 = ranks = None); otherwise the histogram rides in the fused kernel and the ranks its atomics return
+    make the fill atomic-free."""
+    binned_bytes = 0
+    if xs.numel() >= GROUP_BINNED_MIN_PAIRS and not _LOCAL.deterministic_grouping and \
+            N.load().trec_get_tuning(b"group_pairs_binned", 1) != 0:
+        binned_bytes = int(N.query("trec_group_pairs_binned_bytes", int(xs.numel()), int(n_items)))
+    if binned_bytes > 0:
+        return binned_bytes, None, None
+    ws32 = torch.zeros((2 * n_items,), dtype=torch.int32, device=dev)     # [sample histogram | cursors] of the sort below
+    ranks = torch.empty((n_users, S), dtype=torch.int32, device=dev)
+    return binned_bytes, ws32, ranks
+
+
+def _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks):
+    """The item side of a one-pass fused step (wmrb_fused_step, softmax_fused_step): d item_in = G^T . user_in over both pair lists,
+    d b_i = per-item sums of the coefficients -- the static transposed structure for the interactions, the binned or ranked grouping
+    (_fused_sample_grouping) for the samples, the packed K1 gather with the row-sum epilogue.  Returns (d_v, d_ib)."""
+    n_users, n_items = interactions.shape
+    d = u.shape[1]
+    dev = u.device
+    nnz = interactions.nnz
+    # (MEASURED and dropped, profiles/r05_fit_overlap_ab.txt: the sort on a second stream -- whole, next to the fused kernel with
+    # the coefficients read through the pair permutation: 34.4 ms per epoch against 25.7; only its fill, next to the item-side
+    # gather of the interactions: 26.2 against 26.1 -- every kernel of this step is bound by the same fabric, an overlapped pair
+    # slows down by exactly what it hides)
+    d_v = torch.zeros_like(v) if nnz == 0 else None
+    d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
+    # (epilogue 3 of K1: the row sums of the gathered coefficients = d b_i come out of the same pass)
+    epi = EPI_ROWSUM if ib is not None else EPI_NONE
+    rowsum = d_ib if epi == EPI_ROWSUM else None
+    if nnz:
+        indptr_t, users_t, perm_t = interactions.transposed()
+        if interactions.max_col_nnz > SPLIT_T:           # popular items: their pairs are summed as chunks
+            d_v = spmm_split(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, want_rowsum=rowsum)
+        else:
+            d_v = _spmm_rowsum(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, epi, False, None, d_ib)
+    split_samples = xs.numel() > n_items * _SPLIT_MEAN
+    if binned_bytes > 0:
+        ind_s = torch.empty((n_items + 1,), dtype=torch.int64, device=dev)
+        entries = torch.empty((xs.numel(), 2), dtype=torch.int32, device=dev)
+        bws = torch.empty((binned_bytes,), dtype=torch.uint8, device=dev)
+        # a sample whose coefficient is exactly 0 (WMRB: it violates no margin of its user; softmax: an accidental hit, an underflow)
+        # adds nothing to its item's gradient: such pairs are left out of the sort and of the item-side gather (the chunked gather
+        # below is sized by the pair count: all pairs there)
+        drop_zero = 0 if split_samples else int(N.load().trec_get_tuning(b"group_pairs_drop_zero", 1) != 0)
+        with _timed("group_pairs_binned"):
+            N.call("trec_group_pairs_by_item_binned", None, N.ptr(xs), N.ptr(coef_s.reshape(-1)), int(xs.numel()), S, n_items,
+                   drop_zero, N.ptr(bws), binned_bytes, N.ptr(ind_s), N.ptr(entries))
+    else:
+        ind_s, entries, _ = group_pairs_by_item(None, xs, S, n_items, workspace_with_counts=ws32, ranks=ranks.reshape(-1),
+                                                values=coef_s.reshape(-1))
+    # which grouping this call took (host-side facts only: parity records and tests assert the route they mean to cover)
+    LAST_FUSED_STATS["route"] = "binned" if binned_bytes > 0 else "ranked"
+    LAST_FUSED_STATS["drop_zero"] = bool(binned_bytes > 0 and drop_zero)
+    if KERNEL_EVENTS is not None:                        # (measurement runs only: how many sampled pairs the item side still sees)
+        LAST_FUSED_STATS["sampled_pairs"] = int(xs.numel())
+        LAST_FUSED_STATS["sampled_pairs_kept"] = ind_s[-1:].clone()
+        LAST_FUSED_STATS["sampled_pairs_with_coefficient_0"] = (coef_s == 0).sum()
+        LAST_FUSED_STATS["loss_mean"] = loss.mean()
+    if split_samples:                                    # few items: every bucket of samples is long
+        spmm_split(ind_s, None, None, None, n_items, xs.numel(), u, accumulate=True, out=d_v, want_rowsum=rowsum,
+                   packed=entries)
+    else:
+        with _timed("spmm_csr"):
+            N.call("trec_spmm_csr_packed", N.ptr(ind_s), N.ptr(entries), n_items, N.ptr(u), d, epi, 1, N.ptr(d_v),
+                   N.ptr(rowsum))
+    return d_v, d_ib
+
+
 def wmrb_fused_step(user_in, item_in, user_bias, item_bias, interactions, samples, balanced=False):
     """One WMRB / BalancedWMRB step for dot scores on (user_in, item_in), upstream gradient 1 (the trainer minimises
     the SUM of the loss vector): returns (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias).
@@ -896,68 +968,62 @@ def wmrb_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
     weight = interactions.balanced_weight() if balanced else None
     samples = samples.to(torch.int32).contiguous()
     xs = samples.reshape(-1)
-    # very many sampled pairs: grouped by item through a two-level LDS partition that needs no ranks (csrc/segment.hip, "binned") --
-    # the fused kernel then issues no histogram atomics at all; otherwise the histogram rides in the fused kernel and the ranks its
-    # atomics return make the fill atomic-free
-    binned_bytes = 0
-    if xs.numel() >= GROUP_BINNED_MIN_PAIRS and not _LOCAL.deterministic_grouping and \
-            N.load().trec_get_tuning(b"group_pairs_binned", 1) != 0:
-        binned_bytes = int(N.query("trec_group_pairs_binned_bytes", int(xs.numel()), int(n_items)))
-    if binned_bytes > 0:
-        ws32 = ranks = None
-    else:
-        ws32 = torch.zeros((2 * n_items,), dtype=torch.int32, device=dev)     # [sample histogram | cursors] of the sort below
-        ranks = torch.empty((n_users, S), dtype=torch.int32, device=dev)
+    binned_bytes, ws32, ranks = _fused_sample_grouping(xs, n_users, n_items, S, dev)
     with _timed("wmrb_fused_step"):
         N.call("trec_wmrb_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
                N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(weight), N.ptr(samples), n_users,
                n_items, S, d, int(interactions.max_row_nnz), N.ptr(loss), N.ptr(pred), N.ptr(d_u), N.ptr(d_ub),
                N.ptr(coef_s), N.ptr(coef_p), N.ptr(ws32), N.ptr(ranks))
-    # ---- item side: d item_in = G^T . user_in over both pair lists, d b_i = per-item sums of the coefficients
-    # (MEASURED and dropped, profiles/r05_fit_overlap_ab.txt: the sort on a second stream -- whole, next to the fused kernel with
-    # the coefficients read through the pair permutation: 34.4 ms per epoch against 25.7; only its fill, next to the item-side
-    # gather of the interactions: 26.2 against 26.1 -- every kernel of this step is bound by the same fabric, an overlapped pair
-    # slows down by exactly what it hides)
-    d_v = torch.zeros_like(v) if nnz == 0 else None
-    d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
-    # (epilogue 3 of K1: the row sums of the gathered coefficients = d b_i come out of the same pass)
-    epi = EPI_ROWSUM if ib is not None else EPI_NONE
-    rowsum = d_ib if epi == EPI_ROWSUM else None
-    if nnz:
-        indptr_t, users_t, perm_t = interactions.transposed()
-        if interactions.max_col_nnz > SPLIT_T:           # popular items: their pairs are summed as chunks
-            d_v = spmm_split(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, want_rowsum=rowsum)
-        else:
-            d_v = _spmm_rowsum(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, epi, False, None, d_ib)
-    split_samples = xs.numel() > n_items * _SPLIT_MEAN
-    if binned_bytes > 0:
-        ind_s = torch.empty((n_items + 1,), dtype=torch.int64, device=dev)
-        entries = torch.empty((xs.numel(), 2), dtype=torch.int32, device=dev)
-        bws = torch.empty((binned_bytes,), dtype=torch.uint8, device=dev)
-        # a sample that violates no margin of its user has coefficient exactly 0 and adds nothing to its item's gradient: such pairs
-        # are left out of the sort and of the item-side gather (the chunked gather below is sized by the pair count: all pairs there)
-        drop_zero = 0 if split_samples else int(N.load().trec_get_tuning(b"group_pairs_drop_zero", 1) != 0)
-        with _timed("group_pairs_binned"):
-            N.call("trec_group_pairs_by_item_binned", None, N.ptr(xs), N.ptr(coef_s.reshape(-1)), int(xs.numel()), S, n_items,
-                   drop_zero, N.ptr(bws), binned_bytes, N.ptr(ind_s), N.ptr(entries))
-    else:
-        ind_s, entries, _ = group_pairs_by_item(None, xs, S, n_items, workspace_with_counts=ws32, ranks=ranks.reshape(-1),
-                                                values=coef_s.reshape(-1))
-    # which grouping this call took (host-side facts only: parity records and tests assert the route they mean to cover)
-    LAST_FUSED_STATS["route"] = "binned" if binned_bytes > 0 else "ranked"
-    LAST_FUSED_STATS["drop_zero"] = bool(binned_bytes > 0 and drop_zero)
-    if KERNEL_EVENTS is not None:                        # (measurement runs only: how many sampled pairs the item side still sees)
-        LAST_FUSED_STATS["sampled_pairs"] = int(xs.numel())
-        LAST_FUSED_STATS["sampled_pairs_kept"] = ind_s[-1:].clone()
-        LAST_FUSED_STATS["sampled_pairs_with_coefficient_0"] = (coef_s == 0).sum()
-        LAST_FUSED_STATS["loss_mean"] = loss.mean()
-    if split_samples:                                    # few items: every bucket of samples is long
-        spmm_split(ind_s, None, None, None, n_items, xs.numel(), u, accumulate=True, out=d_v, want_rowsum=rowsum,
-                   packed=entries)
-    else:
-        with _timed("spmm_csr"):
-            N.call("trec_spmm_csr_packed", N.ptr(ind_s), N.ptr(entries), n_items, N.ptr(u), d, epi, 1, N.ptr(d_v),
-                   N.ptr(rowsum))
+    d_v, d_ib = _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks)
+    return loss, pred, d_u, d_v, d_ub, d_ib
+
+
+def softmax_fused_supported(n_sampled, interactions, d):
+    """Can the one-pass sampled-softmax step (csrc/softmax_fused.hip) run this shape?  (The coverage of wmrb_fused_supported.)"""
+    if not N.load().trec_get_tuning(b"softmax_fused", 1):
+        return False
+    return N.query("trec_softmax_fused_lds_bytes", int(n_sampled), int(interactions.max_row_nnz), int(d)) >= 0
+
+
+def softmax_fused_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
+                       log_q_correction=False, remove_accidental_hits=False):
+    """One sampled-softmax step for dot scores on (user_in, item_in), upstream gradient 1: wmrb_fused_step with the loss of
+    sampled_softmax_loss (``temperature``, ``sample_log_q``, ``log_q_correction``, ``remove_accidental_hits`` as there).  Returns
+    (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias); the item side is wmrb_fused_step's."""
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
+    ub = _f32c(user_bias.detach()) if user_bias is not None else None
+    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    n_users, n_items = interactions.shape
+    if tuple(samples.shape[:1]) != (n_users,) or samples.dim() != 2:
+        raise ValueError("samples must be an [n_users, n_sampled] table")
+    S = int(samples.shape[1])
+    d = u.shape[1]
+    dev = u.device
+    nnz = interactions.nnz
+    log_q = None
+    if log_q_correction and sample_log_q is not None:
+        if sample_log_q.numel() != n_items:
+            raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
+        log_q = _f32c(sample_log_q).reshape(-1)
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_u = torch.empty_like(u)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    coef_s = torch.empty((n_users, S), dtype=torch.float32, device=dev)
+    coef_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    samples = samples.to(torch.int32).contiguous()
+    xs = samples.reshape(-1)
+    binned_bytes, ws32, ranks = _fused_sample_grouping(xs, n_users, n_items, S, dev)
+    with _timed("softmax_fused_step"):
+        N.call("trec_softmax_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
+               N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(samples), n_users, n_items, S, d,
+               int(interactions.max_row_nnz), 1.0 / temperature, N.ptr(log_q), -math.log(n_items), 1 if log_q_correction else 0,
+               1 if remove_accidental_hits else 0, N.ptr(loss), N.ptr(pred), N.ptr(d_u), N.ptr(d_ub), N.ptr(coef_s), N.ptr(coef_p),
+               N.ptr(ws32), N.ptr(ranks))
+    d_v, d_ib = _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks)
     return loss, pred, d_u, d_v, d_ub, d_ib
 
 

@@ -371,6 +371,8 @@ class TensorRec(object):
         self._store = None
         self._graph_pool_owner = []
         self.last_route = None        # what predict_top_k did last (route report)
+        self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused";
+                                      # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
         self._adam = {}
@@ -799,7 +801,7 @@ class TensorRec(object):
             # serial scores -> loss -> autograd; only the exact built-in classes qualify (subclasses may override)
             # (rows in registers: dot scores, S + the longest row <= 256; otherwise -- S in the thousands, Euclidean scores --
             # the tiled form of the same step, csrc/wmrb_tiled.hip)
-            fused = tiled = False
+            fused = tiled = fused_softmax = False
             if (engine and not multi and graph.engine_mode in (ops.MODE_DOT, ops.MODE_EUCLIDEAN)
                     and type(loss_graph) in (WMRBLossGraph, BalancedWMRBLossGraph)
                     and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
@@ -807,6 +809,12 @@ class TensorRec(object):
                 fused = graph.engine_mode == ops.MODE_DOT and \
                     ops.wmrb_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
                 tiled = not fused and ops.wmrb_tiled_supported(n_sampled_items, inter, int(item_repr.shape[1]))
+            # the built-in sampled softmax on dot / cosine scores: the same one-pass step with its own loss phase
+            # (csrc/softmax_fused.hip); Euclidean scores, subclasses and uncovered shapes take the generic step below
+            elif (engine and not multi and graph.engine_mode == ops.MODE_DOT and type(loss_graph) is SampledSoftmaxLossGraph
+                    and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
+                    and user_reprs[0].shape[1] == item_repr.shape[1]):
+                fused_softmax = ops.softmax_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
             u_ins, a_ins, i_in = user_reprs, attn_reprs, item_repr
             if engine and graph.engine_normalize:     # cosine: normalise once, share between all serial calls
                 u_ins = [ops.l2_normalize_rows(u) for u in user_reprs]
@@ -817,6 +825,10 @@ class TensorRec(object):
                 return self._fused_wmrb_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                              n_sampled_items, want_stats, samples, apply,
                                              tiled_mode=graph.engine_mode if tiled else None)
+            if fused_softmax:
+                return self._fused_softmax_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
+                                                n_sampled_items, want_stats, samples, apply)
+            self.last_step_kernel = None
             if multi:
                 pred_serial = self._serial_multi(u_ins, a_ins, i_in, x_user, x_item, user_bias, item_bias)
             elif engine:
@@ -902,12 +914,36 @@ class TensorRec(object):
             samples = self._draw_samples(inter, n_sampled_items)
         ub = user_bias if self.biased else None
         ib = item_bias if self.biased else None
+        self.last_step_kernel = "wmrb_tiled" if tiled_mode is not None else "wmrb_fused"
         if tiled_mode is not None:
             basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.wmrb_tiled_step(u_in, i_in, ub, ib, inter, samples,
                                                                                 balanced=loss_graph.balanced, mode=tiled_mode)
         else:
             basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.wmrb_fused_step(u_in, i_in, ub, ib, inter, samples,
                                                                                 balanced=loss_graph.balanced)
+        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
+                                       learning_rate, alpha, want_stats, apply)
+
+    def _fused_softmax_step(self, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
+                            want_stats, samples=None, apply=True):
+        """The sampled-softmax step with the user side in one kernel (ops.softmax_fused_step), fed like the generic step: the
+        loss graph's temperature and options, log q from the sampler when it has one."""
+        loss_graph = self.loss_graph_factory
+        if samples is None:
+            samples = self._draw_samples(inter, n_sampled_items)
+        self.last_step_kernel = "softmax_fused"
+        log_q = getattr(self.sampler, 'log_q', None)
+        basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.softmax_fused_step(
+            u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter, samples,
+            loss_graph.temperature, sample_log_q=log_q(self._store.device) if callable(log_q) else None,
+            log_q_correction=loss_graph.log_q_correction, remove_accidental_hits=loss_graph.remove_accidental_hits)
+        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
+                                       learning_rate, alpha, want_stats, apply)
+
+    def _finish_fused_step(self, basic_loss, pred_serial, grads4, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
+                           want_stats, apply):
+        """Hands the gradients of a one-pass step to autograd (K1 backward through the representation graphs) and steps."""
+        d_u, d_v, d_ub, d_ib = grads4
         tensors, grads = [u_in, i_in], [d_u, d_v]
         if self.biased:
             tensors += [user_bias, item_bias]
