@@ -672,6 +672,39 @@ int trec_softmax_fused_step(const float* U, const float* V, const float* user_bi
                             int32_t log_q_correction, int32_t remove_hits, float* loss, float* pred_serial, float* dU,
                             float* d_user_bias, float* coef_samples, float* coef_pairs, int32_t* sample_hist,
                             int32_t* sample_rank, void* stream);
+/* The sampled softmax with ONE set of n_sampled negatives shared by every user of the step (csrc/softmax_shared.hip): the sample rows
+ * are one gathered [n_sampled, d] matrix Vs with biases sample_bias (nullable) and logit constants sample_c (nullable: 0), and
+ * w_us = ((U_u . Vs_s + user_bias_u) + sample_bias_s) inv_temperature + sample_c_s is formed tile by tile on fp32 MFMAs
+ * (v_mfma_f32_32x32x2_f32); nothing of size [n_users, n_sampled] is stored.  Coverage: n_sampled >= 1, d % 4 == 0, 4 <= d <= 128
+ * (trec_softmax_shared_supported: 1 or 0).  No atomics, fixed summation orders: every call is deterministic.
+ *   _stats      M[u] = max_s w_us, Z[u] = sum_s exp(w_us - M[u])  (online over 32-sample tiles; columns past n_sampled enter as -inf).
+ *   _positives  O(P): per interaction with pos_slot >= 0 the loss of trec_sampled_softmax_fwd on (pred_serial inv_temperature, M, Z)
+ *               into loss[pos_slot] and d_pred at upstream gradient 1; pos_slot < 0: d_pred = 0, no loss.  tK[u] = inv_temperature
+ *               K_u (0 for a user without positives); d_user_bias (nullable) [u] = sum_p d_pred_p + tK[u] Z[u].
+ *   _grads      P_us = tK[u] exp(w_us - M[u]):  dU[u] += sum_s P_us Vs_s (dU holds the positives' part on entry), dVs[s] = sum_u P_us
+ *               U_u, d_sample_bias (nullable) [s] = sum_u P_us.  The user range of dVs is cut into n_slices slices whose partial
+ *               products are added in slice order; n_slices must be trec_softmax_shared_slices' answer (tuning
+ *               "softmax_shared_slices" forces a count; otherwise about 1,024 workgroups, at most 256 MiB of partials) and workspace
+ *               (needed from 2 slices on) holds n_slices * n_sampled * (d + 1) floats.
+ *   _scatter    dV[id] += the rows of dVs whose sample has that id, added in slot order, d_item_bias (nullable) likewise:
+ *               sorted_ids [n_sampled] the ids sorted stably, order [n_sampled] the slot of each sorted position; one thread owns
+ *               an id, so duplicate ids are deterministic; ids outside [0, n_items) are skipped.
+ * Errors before any launch: TREC_ERR_INVALID for null pointers, n_sampled < 1, d outside the coverage, an inv_temperature that is
+ * not finite and > 0, a wrong n_slices. */
+int trec_softmax_shared_supported(int32_t n_sampled, int32_t d);
+int trec_softmax_shared_slices(int64_t n_users, int32_t n_sampled, int32_t d);
+int trec_softmax_shared_stats(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                              const float* sample_c, int64_t n_users, int32_t n_sampled, int32_t d, float inv_temperature,
+                              float* M, float* Z, void* stream);
+int trec_softmax_shared_positives(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* M,
+                                  const float* Z, int64_t n_users, float inv_temperature, float* loss, float* d_pred, float* tK,
+                                  float* d_user_bias, void* stream);
+int trec_softmax_shared_grads(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                              const float* sample_c, const float* M, const float* tK, int64_t n_users, int32_t n_sampled,
+                              int32_t d, float inv_temperature, int32_t n_slices, float* workspace, float* dU, float* dVs,
+                              float* d_sample_bias, void* stream);
+int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int64_t* order, const float* dVs, const float* d_sample_bias,
+                                int32_t n_sampled, int32_t d, int64_t n_items, float* dV, float* d_item_bias, void* stream);
 /* The same step for S in the thousands, long interaction rows and Euclidean scores (csrc/wmrb_tiled.hip): the user's S + n_u item
  * rows are streamed twice in tiles (scores into LDS, then the coefficient-weighted sum dU) instead of living in registers.
  * mode 0: dot scores (prediction_graphs.py:52-55; cosine = dot on normalised rows, :70-72); mode 1: euclidean,

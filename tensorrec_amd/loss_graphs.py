@@ -123,16 +123,20 @@ class SampledSoftmaxLossGraph(AbstractLossGraph):
     per user, shared by the user's positives).  ``log_q_correction=True``: every kept sample's logit gets -log(S q(item)), q the
     sampler's probability (``sampler.log_q``; a sampler without that method is taken as uniform): the importance-sampling estimate of
     the full softmax's partition function for S independent draws -- meant for samplers that draw WITH replacement (PopularitySampler).
-    With both off (the default) a step is the plain loss's, bit for bit.  docs/sampled_losses.md.
+    With both off (the default) a step is the plain loss's, bit for bit.  ``shared_negatives=True``: ONE row of S samples is drawn per
+    optimiser step and shared by every user of the batch -- by definition the step fed a table whose rows all equal that row; on
+    dot / cosine scores it runs as MFMA tiles (csrc/softmax_shared.hip) and S may be in the thousands.  docs/sampled_losses.md.
     """
     is_sample_based = True
     is_sampled_with_replacement = False
 
     log_q_correction = remove_accidental_hits = False            # (models pickled before the options existed)
+    shared_negatives = False                                     # (likewise)
 
-    def __init__(self, temperature=1.0, log_q_correction=False, remove_accidental_hits=False):
+    def __init__(self, temperature=1.0, log_q_correction=False, remove_accidental_hits=False, shared_negatives=False):
         self.log_q_correction = _as_bool("log_q_correction", log_q_correction)
         self.remove_accidental_hits = _as_bool("remove_accidental_hits", remove_accidental_hits)
+        self.shared_negatives = _as_bool("shared_negatives", shared_negatives)
         self.wants_sample_items = self.log_q_correction or self.remove_accidental_hits
         try:
             temperature = float(temperature)

@@ -1027,7 +1027,104 @@ def softmax_fused_step(user_in, item_in, user_bias, item_bias, interactions, sam
     return loss, pred, d_u, d_v, d_ub, d_ib
 
 
-DENSE_G_MIN_DENSITY = 1.0 / 32.0      # pairs per user / items from which the item side of the tiled step is a GEMM (G^T . U)
+SOFTMAX_SHARED_DEFAULT = 1       # tuning "softmax_shared" when nobody set it (docs/sampled_losses.md, "Shared negatives": the measurement)
+SOFTMAX_SHARED_MAX_D = 128
+
+
+def _f32r(x):
+    """x rounded to float32, as a Python float"""
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def softmax_shared_supported(n_sampled, interactions, d):
+    """Can the shared-negatives MFMA step (csrc/softmax_shared.hip) run this shape?  n_sampled >= 1, d % 4 == 0, 4 <= d <= 128; the
+    interactions do not restrict it (the positives are O(P) work on K3's scores).  Tuning ``softmax_shared = 0`` answers False."""
+    if not N.load().trec_get_tuning(b"softmax_shared", SOFTMAX_SHARED_DEFAULT):
+        return False
+    return bool(N.query("trec_softmax_shared_supported", int(n_sampled), int(d)))
+
+
+def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
+                        log_q_correction=False):
+    """One sampled-softmax step for dot scores on (user_in, item_in) whose ``samples`` -- int32 [S] -- are shared by every user: the
+    step softmax_fused_step would make of the [n_users, S] table that repeats them, accidental hits kept, upstream gradient 1.
+    Returns (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias).  The [U, S] logits exist only as MFMA
+    tiles: row statistics, then the positives (K3 scores, O(P)), then the samples' gradients in both directions; the [S, d] sample
+    gradient reaches d item_in through a stable sort of the ids (duplicates are added in slot order).  Nothing is read on the host."""
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
+    ub = _f32c(user_bias.detach()) if user_bias is not None else None
+    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    n_users, n_items = interactions.shape
+    if samples.dim() != 1 or samples.numel() < 1:
+        raise ValueError("samples must be a vector of n_sampled >= 1 item ids")
+    S = int(samples.numel())
+    d = int(u.shape[1])
+    if not N.query("trec_softmax_shared_supported", S, d):
+        raise ValueError("softmax_shared_step covers d %% 4 == 0, 4 <= d <= %d; got d = %d" % (SOFTMAX_SHARED_MAX_D, d))
+    dev = u.device
+    nnz = interactions.nnz
+    inv_t = 1.0 / temperature
+    samples = samples.to(torch.int32).contiguous()
+    ids = samples.long()
+    vs = v.index_select(0, ids)                                   # the [S, d] operand, 2 MB at S = 4096
+    bs = ib.index_select(0, ids) if ib is not None else None
+    cs = None
+    if log_q_correction:
+        if sample_log_q is not None:
+            if sample_log_q.numel() != n_items:
+                raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
+            cs = -(_f32c(sample_log_q).reshape(-1).index_select(0, ids) + _f32r(math.log(S)))
+        else:
+            cs = torch.full((S,), -_f32r(_f32r(math.log(S)) + _f32r(-math.log(n_items))), dtype=torch.float32, device=dev)
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    d_vs = torch.empty((S, d), dtype=torch.float32, device=dev)
+    d_bs = torch.empty((S,), dtype=torch.float32, device=dev) if ib is not None else None
+    with _timed("softmax_shared_stats"):
+        N.call("trec_softmax_shared_stats", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), n_users, S, d, inv_t,
+               N.ptr(stat_m), N.ptr(stat_z))
+    # ---- the positives: K3 scores, the loss and d y_p per interaction, K_u per user; their gradients on K3's backward routes
+    if nnz:
+        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
+               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
+    N.call("trec_softmax_shared_positives", N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
+           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
+    d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
+    if nnz:
+        if interactions.max_row_nnz > SPLIT_T:
+            d_u = spmm_split(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
+        else:
+            d_u = spmm_raw(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
+        indptr_t, users_t, perm_t = interactions.transposed()
+        epi = EPI_ROWSUM if ib is not None else EPI_NONE
+        if interactions.max_col_nnz > SPLIT_T:
+            d_v = spmm_split(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, want_rowsum=d_ib if ib is not None else None)
+        else:
+            d_v = _spmm_rowsum(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, epi, False, None, d_ib)
+    else:
+        d_u, d_v = torch.zeros_like(u), torch.zeros_like(v)
+    # ---- the samples: dU += P . Vs, dVs = P^T . U in slices of the users, d b_s = the row sums
+    n_slices = int(N.query("trec_softmax_shared_slices", n_users, S, d))
+    ws = torch.empty((n_slices * S * (d + 1),), dtype=torch.float32, device=dev) if n_slices > 1 else None
+    with _timed("softmax_shared_grads"):
+        N.call("trec_softmax_shared_grads", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), N.ptr(stat_m), N.ptr(t_k),
+               n_users, S, d, inv_t, n_slices, N.ptr(ws), N.ptr(d_u), N.ptr(d_vs), N.ptr(d_bs))
+    sorted_ids, order = torch.sort(samples, stable=True)
+    N.call("trec_softmax_shared_scatter", N.ptr(sorted_ids.contiguous()), N.ptr(order.contiguous()), N.ptr(d_vs), N.ptr(d_bs), S, d,
+           n_items, N.ptr(d_v), N.ptr(d_ib))
+    return loss, pred, d_u, d_v, d_ub, d_ib
+
+
+DENSE_G_MIN_DENSITY = 1.0 / 32.0     # pairs per user / items from which the item side of the tiled step is a GEMM (G^T . U)
 
 
 def wmrb_tiled_supported(n_sampled, interactions, d):

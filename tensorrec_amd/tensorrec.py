@@ -371,7 +371,8 @@ class TensorRec(object):
         self._store = None
         self._graph_pool_owner = []
         self.last_route = None        # what predict_top_k did last (route report)
-        self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused";
+        self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused",
+                                      # "softmax_shared";
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -761,6 +762,8 @@ class TensorRec(object):
     def _graph_eligible(self, inter, n_sampled_items, verbose):
         if not self.hip_graphs or self._dp_active() or self._capture is not None or getattr(self, 'deterministic', False):
             return False
+        if self._shared_negatives():          # one row of samples per step: eager steps only (docs/sampled_losses.md)
+            return False
         # only steps made of the library's own launches are captured: the built-in losses on built-in graphs.  User-defined
         # torch graphs / losses may do anything (host syncs, allocations the capture cannot follow) -- capturing them would
         # fail, warn and fall back on every fit call.
@@ -772,13 +775,21 @@ class TensorRec(object):
         dense = self.loss_graph_factory.is_dense
         return pairs <= 4_000_000 and (not dense or inter.shape[0] * inter.shape[1] <= 4_000_000)
 
+    def _shared_negatives(self):
+        """The loss graph asks for ONE row of samples per step, shared by every user (SampledSoftmaxLossGraph(shared_negatives=True))."""
+        loss_graph = self.loss_graph_factory
+        return bool(loss_graph.is_sample_based and getattr(loss_graph, 'shared_negatives', False))
+
     def _draw_samples(self, inter, n_sampled_items):
-        """tf.py_func(sample_items) of tensorrec.py:298-302: one [n_users, n_sampled_items] int32 table per step."""
+        """tf.py_func(sample_items) of tensorrec.py:298-302: one [n_users, n_sampled_items] int32 table per step -- or, with shared
+        negatives, ONE [1, n_sampled_items] row: the stream of user 0 on every batch and every rank, so a data-parallel fit draws
+        the set a single process would."""
         n_users, n_items = inter.shape
         self._sample_step += 1
-        samples = self.sampler.sample(n_items, n_users, int(n_sampled_items),
+        shared = self._shared_negatives()
+        samples = self.sampler.sample(n_items, 1 if shared else n_users, int(n_sampled_items),
                                       self.loss_graph_factory.is_sampled_with_replacement, self._sample_step,
-                                      self._store.device, getattr(inter, 'user_base', 0))
+                                      self._store.device, 0 if shared else getattr(inter, 'user_base', 0))
         return samples.to(torch.int32).contiguous()
 
     def _train_step(self, inter, user_feats, item_feats, learning_rate, alpha, n_sampled_items, want_stats=False,
@@ -801,7 +812,8 @@ class TensorRec(object):
             # serial scores -> loss -> autograd; only the exact built-in classes qualify (subclasses may override)
             # (rows in registers: dot scores, S + the longest row <= 256; otherwise -- S in the thousands, Euclidean scores --
             # the tiled form of the same step, csrc/wmrb_tiled.hip)
-            fused = tiled = fused_softmax = False
+            fused = tiled = fused_softmax = shared_mfma = False
+            shared = self._shared_negatives()
             if (engine and not multi and graph.engine_mode in (ops.MODE_DOT, ops.MODE_EUCLIDEAN)
                     and type(loss_graph) in (WMRBLossGraph, BalancedWMRBLossGraph)
                     and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
@@ -814,7 +826,12 @@ class TensorRec(object):
             elif (engine and not multi and graph.engine_mode == ops.MODE_DOT and type(loss_graph) is SampledSoftmaxLossGraph
                     and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
                     and user_reprs[0].shape[1] == item_repr.shape[1]):
-                fused_softmax = ops.softmax_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
+                if not shared:
+                    fused_softmax = ops.softmax_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
+                elif not loss_graph.remove_accidental_hits:
+                    # one shared row of samples: the [U, S] logits as MFMA tiles (csrc/softmax_shared.hip); hits removed, Euclidean
+                    # scores, subclasses and uncovered d expand the row and take the generic step below, never the per-user fused one
+                    shared_mfma = ops.softmax_shared_supported(n_sampled_items, inter, int(item_repr.shape[1]))
             u_ins, a_ins, i_in = user_reprs, attn_reprs, item_repr
             if engine and graph.engine_normalize:     # cosine: normalise once, share between all serial calls
                 u_ins = [ops.l2_normalize_rows(u) for u in user_reprs]
@@ -828,6 +845,9 @@ class TensorRec(object):
             if fused_softmax:
                 return self._fused_softmax_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                                 n_sampled_items, want_stats, samples, apply)
+            if shared_mfma:
+                return self._shared_softmax_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
+                                                 n_sampled_items, want_stats, samples, apply)
             self.last_step_kernel = None
             if multi:
                 pred_serial = self._serial_multi(u_ins, a_ins, i_in, x_user, x_item, user_bias, item_bias)
@@ -866,6 +886,8 @@ class TensorRec(object):
             if loss_graph.is_sample_based:
                 if samples is None:
                     samples = self._draw_samples(inter, n_sampled_items)
+                if shared and samples.shape[0] == 1 and n_users != 1:
+                    samples = samples.expand(n_users, samples.shape[1]).contiguous()     # the definition: every row is the shared one
                 if engine:
                     xs_item = PairIndex.make(samples.reshape(-1), samples.reshape(-1), int(n_sampled_items))
                     if multi:
@@ -937,6 +959,22 @@ class TensorRec(object):
             u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter, samples,
             loss_graph.temperature, sample_log_q=log_q(self._store.device) if callable(log_q) else None,
             log_q_correction=loss_graph.log_q_correction, remove_accidental_hits=loss_graph.remove_accidental_hits)
+        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
+                                       learning_rate, alpha, want_stats, apply)
+
+    def _shared_softmax_step(self, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
+                             want_stats, samples=None, apply=True):
+        """The sampled-softmax step with ONE row of samples for the whole batch (ops.softmax_shared_step): the loss graph's
+        temperature and logQ option, log q from the sampler when it has one."""
+        loss_graph = self.loss_graph_factory
+        if samples is None:
+            samples = self._draw_samples(inter, n_sampled_items)
+        self.last_step_kernel = "softmax_shared"
+        log_q = getattr(self.sampler, 'log_q', None)
+        basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.softmax_shared_step(
+            u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter, samples[0],
+            loss_graph.temperature, sample_log_q=log_q(self._store.device) if callable(log_q) else None,
+            log_q_correction=loss_graph.log_q_correction)
         return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
                                        learning_rate, alpha, want_stats, apply)
 
