@@ -866,11 +866,61 @@ GROUP_BINNED_MIN_PAIRS = int(_os.environ.get("TREC_BINNED_MIN_PAIRS", 1 << 22)) 
                                                                                      # 1M x 1M has 1.25e7 pairs: 3.91 vs 4.10 ms per step)
 
 
+def step_switch(name):
+    """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT.)"""
+    return N.load().trec_get_tuning(name.encode(), SOFTMAX_SHARED_DEFAULT if name == "softmax_shared" else 1) != 0
+
+
+def step_covers(kernel, n_sampled, max_row_nnz, d):
+    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_shared") cover this shape?  The ONE
+    statement of the coverage: the native library's shape query (host arithmetic, needs no GPU); step_plan.kernel and the
+    ``*_supported`` functions below both ask here."""
+    if kernel == "softmax_shared":         # (the interactions do not restrict it: the positives are O(P) work on K3's scores)
+        return bool(N.query("trec_softmax_shared_supported", int(n_sampled), int(d)))
+    return N.query("trec_%s_lds_bytes" % kernel, int(n_sampled), int(max_row_nnz), int(d)) >= 0
+
+
+def _step_supported(kernel, n_sampled, interactions, d):
+    return step_switch(kernel) and step_covers(kernel, n_sampled, interactions.max_row_nnz, d)
+
+
 def wmrb_fused_supported(n_sampled, interactions, d):
-    """Can the one-pass WMRB step (csrc/wmrb_fused.hip) run this shape?  (LDS holds S + max interactions-per-user rows.)"""
-    if not N.load().trec_get_tuning(b"wmrb_fused", 1):
-        return False
-    return N.query("trec_wmrb_fused_lds_bytes", int(n_sampled), int(interactions.max_row_nnz), int(d)) >= 0
+    """Can the one-pass WMRB step (csrc/wmrb_fused.hip) run this shape, and is tuning ``wmrb_fused`` on?"""
+    return _step_supported("wmrb_fused", n_sampled, interactions, d)
+
+
+def _step_operands(user_in, item_in, user_bias, item_bias):
+    """(u, v, ub, ib) of a one-pass step: detached, float32, contiguous; absent biases stay None."""
+    return tuple(_f32c(x.detach()) if x is not None else None for x in (user_in, item_in, user_bias, item_bias))
+
+
+def _checked_temperature(temperature):
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+    return temperature
+
+
+def _checked_log_q(sample_log_q, n_items):
+    if sample_log_q.numel() != n_items:
+        raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
+    return _f32c(sample_log_q).reshape(-1)
+
+
+def _fused_step_buffers(u, ub, interactions, samples):
+    """What both per-user fused steps allocate: (loss [P+], pred [P], d_u, d_ub or None, coef_s [U, S], coef_p [P], the int32 sample
+    table, the same flattened, _fused_sample_grouping's triple)."""
+    n_users, n_items = interactions.shape
+    S, dev, nnz = int(samples.shape[1]), u.device, interactions.nnz
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_u = torch.empty_like(u)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    coef_s = torch.empty((n_users, S), dtype=torch.float32, device=dev)
+    coef_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    samples = samples.to(torch.int32).contiguous()
+    xs = samples.reshape(-1)
+    return loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, _fused_sample_grouping(xs, n_users, n_items, S, dev)
 
 
 def _fused_sample_grouping(xs, n_users, n_items, S, dev):
@@ -951,24 +1001,11 @@ def wmrb_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
     The user side -- predictions of the interactions and of the sampled pairs, loss, dU, d b_u -- is one kernel with
     every item row gathered once; the item side groups the per-pair coefficients by item (static transposed structure
     for the interactions, device counting sort for the samples) and runs the segmented K1 gathers / segment sums."""
-    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
-    ub = _f32c(user_bias.detach()) if user_bias is not None else None
-    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
-    S = int(samples.shape[1])
-    d = u.shape[1]
-    dev = u.device
-    nnz = interactions.nnz
-    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
-    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    d_u = torch.empty_like(u)
-    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
-    coef_s = torch.empty((n_users, S), dtype=torch.float32, device=dev)
-    coef_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    S, d = int(samples.shape[1]), u.shape[1]
+    loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = _fused_step_buffers(u, ub, interactions, samples)
     weight = interactions.balanced_weight() if balanced else None
-    samples = samples.to(torch.int32).contiguous()
-    xs = samples.reshape(-1)
-    binned_bytes, ws32, ranks = _fused_sample_grouping(xs, n_users, n_items, S, dev)
     with _timed("wmrb_fused_step"):
         N.call("trec_wmrb_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
                N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(weight), N.ptr(samples), n_users,
@@ -979,10 +1016,8 @@ def wmrb_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
 
 
 def softmax_fused_supported(n_sampled, interactions, d):
-    """Can the one-pass sampled-softmax step (csrc/softmax_fused.hip) run this shape?  (The coverage of wmrb_fused_supported.)"""
-    if not N.load().trec_get_tuning(b"softmax_fused", 1):
-        return False
-    return N.query("trec_softmax_fused_lds_bytes", int(n_sampled), int(interactions.max_row_nnz), int(d)) >= 0
+    """Can the one-pass sampled-softmax step (csrc/softmax_fused.hip) run this shape, and is tuning ``softmax_fused`` on?"""
+    return _step_supported("softmax_fused", n_sampled, interactions, d)
 
 
 def softmax_fused_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
@@ -990,33 +1025,14 @@ def softmax_fused_step(user_in, item_in, user_bias, item_bias, interactions, sam
     """One sampled-softmax step for dot scores on (user_in, item_in), upstream gradient 1: wmrb_fused_step with the loss of
     sampled_softmax_loss (``temperature``, ``sample_log_q``, ``log_q_correction``, ``remove_accidental_hits`` as there).  Returns
     (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias); the item side is wmrb_fused_step's."""
-    temperature = float(temperature)
-    if not (temperature > 0.0 and temperature != float("inf")):
-        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
-    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
-    ub = _f32c(user_bias.detach()) if user_bias is not None else None
-    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    temperature = _checked_temperature(temperature)
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
     if tuple(samples.shape[:1]) != (n_users,) or samples.dim() != 2:
         raise ValueError("samples must be an [n_users, n_sampled] table")
-    S = int(samples.shape[1])
-    d = u.shape[1]
-    dev = u.device
-    nnz = interactions.nnz
-    log_q = None
-    if log_q_correction and sample_log_q is not None:
-        if sample_log_q.numel() != n_items:
-            raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
-        log_q = _f32c(sample_log_q).reshape(-1)
-    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
-    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    d_u = torch.empty_like(u)
-    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
-    coef_s = torch.empty((n_users, S), dtype=torch.float32, device=dev)
-    coef_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    samples = samples.to(torch.int32).contiguous()
-    xs = samples.reshape(-1)
-    binned_bytes, ws32, ranks = _fused_sample_grouping(xs, n_users, n_items, S, dev)
+    S, d = int(samples.shape[1]), u.shape[1]
+    log_q = _checked_log_q(sample_log_q, n_items) if log_q_correction and sample_log_q is not None else None
+    loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = _fused_step_buffers(u, ub, interactions, samples)
     with _timed("softmax_fused_step"):
         N.call("trec_softmax_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
                N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(samples), n_users, n_items, S, d,
@@ -1038,11 +1054,8 @@ def _f32r(x):
 
 
 def softmax_shared_supported(n_sampled, interactions, d):
-    """Can the shared-negatives MFMA step (csrc/softmax_shared.hip) run this shape?  n_sampled >= 1, d % 4 == 0, 4 <= d <= 128; the
-    interactions do not restrict it (the positives are O(P) work on K3's scores).  Tuning ``softmax_shared = 0`` answers False."""
-    if not N.load().trec_get_tuning(b"softmax_shared", SOFTMAX_SHARED_DEFAULT):
-        return False
-    return bool(N.query("trec_softmax_shared_supported", int(n_sampled), int(d)))
+    """Can the shared-negatives MFMA step (csrc/softmax_shared.hip) run this shape, and is tuning ``softmax_shared`` on?"""
+    return _step_supported("softmax_shared", n_sampled, interactions, d)
 
 
 def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
@@ -1052,21 +1065,14 @@ def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, sa
     Returns (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias).  The [U, S] logits exist only as MFMA
     tiles: row statistics, then the positives (K3 scores, O(P)), then the samples' gradients in both directions; the [S, d] sample
     gradient reaches d item_in through a stable sort of the ids (duplicates are added in slot order).  Nothing is read on the host."""
-    temperature = float(temperature)
-    if not (temperature > 0.0 and temperature != float("inf")):
-        raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
-    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
-    ub = _f32c(user_bias.detach()) if user_bias is not None else None
-    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    temperature = _checked_temperature(temperature)
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
     if samples.dim() != 1 or samples.numel() < 1:
         raise ValueError("samples must be a vector of n_sampled >= 1 item ids")
-    S = int(samples.numel())
-    d = int(u.shape[1])
-    if not N.query("trec_softmax_shared_supported", S, d):
+    S, d, dev, nnz = int(samples.numel()), int(u.shape[1]), u.device, interactions.nnz
+    if not step_covers("softmax_shared", S, 0, d):
         raise ValueError("softmax_shared_step covers d %% 4 == 0, 4 <= d <= %d; got d = %d" % (SOFTMAX_SHARED_MAX_D, d))
-    dev = u.device
-    nnz = interactions.nnz
     inv_t = 1.0 / temperature
     samples = samples.to(torch.int32).contiguous()
     ids = samples.long()
@@ -1075,9 +1081,7 @@ def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, sa
     cs = None
     if log_q_correction:
         if sample_log_q is not None:
-            if sample_log_q.numel() != n_items:
-                raise ValueError("sample_log_q has %d entries, the interactions %d items" % (sample_log_q.numel(), n_items))
-            cs = -(_f32c(sample_log_q).reshape(-1).index_select(0, ids) + _f32r(math.log(S)))
+            cs = -(_checked_log_q(sample_log_q, n_items).index_select(0, ids) + _f32r(math.log(S)))
         else:
             cs = torch.full((S,), -_f32r(_f32r(math.log(S)) + _f32r(-math.log(n_items))), dtype=torch.float32, device=dev)
     loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
@@ -1128,10 +1132,9 @@ DENSE_G_MIN_DENSITY = 1.0 / 32.0     # pairs per user / items from which the ite
 
 
 def wmrb_tiled_supported(n_sampled, interactions, d):
-    """Can the tiled one-pass WMRB step (csrc/wmrb_tiled.hip: any S, dot or Euclidean scores) run this shape?"""
-    if not N.load().trec_get_tuning(b"wmrb_tiled", 1):
-        return False
-    return N.query("trec_wmrb_tiled_lds_bytes", int(n_sampled), int(interactions.max_row_nnz), int(d)) >= 0
+    """Can the tiled one-pass WMRB step (csrc/wmrb_tiled.hip: any S, dot or Euclidean scores) run this shape, and is tuning
+    ``wmrb_tiled`` on?"""
+    return _step_supported("wmrb_tiled", n_sampled, interactions, d)
 
 
 def _dense_g_fits(n_users, n_items, n_sampled, nnz, dev):
@@ -1157,14 +1160,9 @@ def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, sample
     then dU).  Item side: when a user's pairs are a sizeable share of the catalogue (configs[4]: 10 %), the pairs' values were
     also added into a dense G [n_users, n_items] and d item_in is G^T . U on fp32 MFMA -- no sort, no second gather of 3.7e8
     rows; otherwise the grouped gathers of the composed path (transposed interactions + counting sort of the samples)."""
-    u, v = _f32c(user_in.detach()), _f32c(item_in.detach())
-    ub = _f32c(user_bias.detach()) if user_bias is not None else None
-    ib = _f32c(item_bias.detach()) if item_bias is not None else None
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
-    S = int(samples.shape[1])
-    d = u.shape[1]
-    dev = u.device
-    nnz = interactions.nnz
+    S, d, dev, nnz = int(samples.shape[1]), u.shape[1], u.device, interactions.nnz
     euclid = mode == MODE_EUCLIDEAN
     loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
     pred = torch.empty((nnz,), dtype=torch.float32, device=dev)

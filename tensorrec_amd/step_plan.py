@@ -1,0 +1,93 @@
+"""
+EXTENSION: which kernel and which launch form a training step takes -- decided on the host from numbers alone: nothing here launches a
+kernel, touches torch's device state or runs a collective, so the route table is checked without a GPU (tests/test_step_plan_host.py).
+``kernel`` names the one-pass step kernel (TensorRec.last_step_kernel), ``coop_covered`` and ``graph_eligible`` decide the launch form
+(TensorRec.last_step_form: "coop", then "graph", then "eager" -- TensorRec._run_epochs asks in that order).  TensorRec._train_step,
+_CoopStep.plan and TensorRec._graph_eligible gather the inputs; the shapes a kernel covers are ops.step_covers' to say.
+"""
+from collections import namedtuple
+
+from . import ops
+from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph
+
+Switches = namedtuple("Switches", "wmrb_fused wmrb_tiled softmax_fused softmax_shared fit_step_coop")
+# only the exact built-in classes have a kind: a subclass may override anything the kernels restate
+LOSS_KINDS = {WMRBLossGraph: "wmrb", BalancedWMRBLossGraph: "balanced_wmrb", SampledSoftmaxLossGraph: "sampled_softmax"}
+WMRB_KINDS = ("wmrb", "balanced_wmrb")
+MAX_GRAPHED_PAIRS = 4_000_000   # interactions + sampled pairs (and U * I of a dense loss) up to which a step is launch-bound
+MAX_GRAPHED_BATCHES = 64        # graphs kept alive by one fit call; further batches run eagerly
+
+
+def read_switches():
+    """The five tunings the choice reads (``softmax_shared`` defaults to ops.SOFTMAX_SHARED_DEFAULT, the others on) as the native
+    library holds them now; needs no GPU."""
+    return Switches(*(ops.step_switch(name) for name in Switches._fields))
+
+
+def loss_kind(loss_graph):
+    """"wmrb", "balanced_wmrb", "sampled_softmax" for an instance of exactly that built-in class, None for everything else."""
+    return LOSS_KINDS.get(type(loss_graph))
+
+
+def kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz, d, shared_negatives, remove_accidental_hits,
+           switches=None):
+    """The one-pass kernel of a training step -- "wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_shared" -- or None: the generic
+    step (serial scores -> loss graph -> autograd).  ``loss``: loss_kind's answer; ``engine`` / ``engine_mode``: the prediction graph
+    is a built-in one, and its mode; ``multi``: several tastes; ``same_width``: both representations are 2-D and equally wide, ``d``
+    that width; ``max_row_nnz``: the longest interaction row of the batch; ``switches``: a Switches, None reads the library's."""
+    if not engine or multi or n_sampled is None or not same_width or loss is None:
+        return None
+
+    def covered(name):              # (the library's switches are read one at a time, as they are asked for: this runs every step)
+        on = ops.step_switch(name) if switches is None else getattr(switches, name)
+        return on and ops.step_covers(name, n_sampled, max_row_nnz, d)
+    # built-in WMRB: one fused pass per user with the rows in registers (dot / cosine scores, csrc/wmrb_fused.hip); otherwise -- S in
+    # the thousands, long rows, Euclidean scores -- the tiled form of the same step (csrc/wmrb_tiled.hip)
+    if loss in WMRB_KINDS and engine_mode in (ops.MODE_DOT, ops.MODE_EUCLIDEAN):
+        if engine_mode == ops.MODE_DOT and covered("wmrb_fused"):
+            return "wmrb_fused"
+        return "wmrb_tiled" if covered("wmrb_tiled") else None
+    # the built-in sampled softmax on dot / cosine scores: the same one-pass step with its own loss phase (csrc/softmax_fused.hip).
+    # One shared row of samples: the [U, S] logits as MFMA tiles (csrc/softmax_shared.hip); with hits removed or an uncovered d the
+    # row is expanded for the generic step, never for the per-user fused one.
+    if loss == "sampled_softmax" and engine_mode == ops.MODE_DOT:
+        if not shared_negatives:
+            return "softmax_fused" if covered("softmax_fused") else None
+        return "softmax_shared" if not remove_accidental_hits and covered("softmax_shared") else None
+    return None
+
+
+def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,
+                   n_items, n_sampled, dense_loss):
+    """May this batch's step be captured in a HIP graph and replayed?  Single process, no gradient capture, no deterministic grouping;
+    shared negatives draw one row per step and stay eager (docs/sampled_losses.md); only steps made of the library's own launches are
+    captured (``loss_capturable``: a built-in loss class, ``engine_graph``: a built-in prediction graph -- user-defined torch code may
+    sync or allocate, capturing it would fail, warn and fall back on every fit call); ``n_graphs`` graphs are held already; and the
+    step is small enough to be bound by its launches."""
+    if not hip_graphs or dp or capturing or deterministic or shared_negatives or not loss_capturable or not engine_graph:
+        return False
+    if n_graphs >= MAX_GRAPHED_BATCHES:
+        return False
+    pairs = nnz + n_users * int(n_sampled or 0)
+    return pairs <= MAX_GRAPHED_PAIRS and (not dense_loss or n_users * n_items <= MAX_GRAPHED_PAIRS)
+
+
+def coop_covered(dp, capturing, deterministic, multi, attention, linear_user, linear_item, dot_product, wmrb, identity_users,
+                 n_user_rows, n_users, n_items, d, n_sampled, max_row_nnz, switches=None):
+    """The stateless part of "does the whole step run as ONE cooperative kernel" (csrc/step_coop.hip): single process, one taste, no
+    attention, Linear representations on both sides (the four graph classes arrive as booleans: exact built-in classes only),
+    DotProduct, WMRB / BalancedWMRB, identity user features with one row per user, n_sampled <= n_items, and a model the kernel's
+    workspace query accepts.  What the variable store and the Adam slots must look like is state: _CoopStep.plan checks it."""
+    sw = read_switches() if switches is None else switches
+    if not sw.fit_step_coop or dp or capturing or deterministic or multi or attention:
+        return False
+    if not (linear_user and linear_item and dot_product and wmrb) or not n_sampled:
+        return False
+    if not identity_users or n_user_rows != n_users or int(n_sampled) > n_items:
+        return False
+    return coop_workspace_floats(n_users, n_items, d, n_sampled, max_row_nnz) >= 0
+
+
+def coop_workspace_floats(n_users, n_items, d, n_sampled, max_row_nnz):
+    """float32 entries of the cooperative step's workspace, -1 for a model it does not cover (host arithmetic of the library)."""
+    return int(ops.N.query("trec_fit_step_coop_workspace_floats", int(n_users), int(n_items), int(d), int(n_sampled), int(max_row_nnz)))

@@ -29,6 +29,7 @@ from scipy import sparse as sp
 from . import ops
 from . import exclusion as _excl
 from . import topk_plan
+from . import step_plan
 from . import similar as _sim
 from . import candidate_sets as _cand
 from . import _native as N
@@ -202,12 +203,18 @@ class ReplaySampler(object):
         return torch.from_numpy(table).to(device)
 
 
-def _adam_lr_t(lr, t):
-    """lr * sqrt(1 - b2^t) / (1 - b1^t) with the float32 running powers TF keeps [external]."""
-    b1p, b2p = np.float32(1.0), np.float32(1.0)
-    for _ in range(int(t)):
+def _beta_powers(t, start=None):
+    """(beta1^t, beta2^t) as the float32 running products TF keeps [external]; ``start``: (t0, beta1^t0, beta2^t0) to go on from."""
+    t0, b1p, b2p = start or (0, np.float32(1.0), np.float32(1.0))
+    for _ in range(int(t) - t0):
         b1p = np.float32(b1p * np.float32(ADAM_BETA1))
         b2p = np.float32(b2p * np.float32(ADAM_BETA2))
+    return b1p, b2p
+
+
+def _adam_lr_t(lr, t, powers=None):
+    """lr * sqrt(1 - b2^t) / (1 - b1^t) with the float32 running powers of _beta_powers (``powers``: those of ``t``, when at hand)."""
+    b1p, b2p = powers or _beta_powers(t)
     return float(np.float32(np.float32(lr) * np.sqrt(np.float32(1.0) - b2p) / (np.float32(1.0) - b1p)))
 
 
@@ -709,26 +716,19 @@ class TensorRec(object):
                 coop = coops.get(batch) if coops is not None else None
                 if coop is None and coops is not None and batch not in coops and (epoch >= 1 or self._opt_step > 0):
                     coop = coops[batch] = _CoopStep.plan(self, inter, uf, itf, n_sampled_items)
-                if coop is not None and coop.ok:
-                    out = coop.run(self, learning_rate, batched_alpha, verbose)
-                    if out is not False:
-                        self.last_step_form = "coop"
-                        loss, serial_predictions, wr_loss = out
-                        if verbose:
-                            logging.info('EPOCH {} BATCH {} loss = {}, weight_reg_l2_loss = {}, mean_pred = {}'.format(
-                                epoch, batch, float(loss.mean()), alpha * wr_loss, float(serial_predictions.mean())))
-                        continue
-                step = graphed.get(batch)
-                if step is None and epoch >= 1 and epochs - epoch >= 2 and batch not in graphed and \
-                        self._graph_eligible(inter, n_sampled_items, verbose):
-                    step = graphed[batch] = _GraphedStep.capture(self, inter, uf, itf, n_sampled_items, learning_rate,
-                                                                 batched_alpha)
-                self.last_step_form = "graph" if step else "eager"
-                if step:
-                    loss, serial_predictions, wr_loss = step.run(self, verbose)
+                out = coop.run(self, learning_rate, batched_alpha, verbose) if coop is not None and coop.ok else False
+                if out is not False:
+                    self.last_step_form = "coop"
                 else:
-                    loss, serial_predictions, wr_loss = self._train_step(inter, uf, itf, learning_rate, batched_alpha,
-                                                                         n_sampled_items, want_stats=verbose)
+                    step = graphed.get(batch)
+                    if step is None and epoch >= 1 and epochs - epoch >= 2 and batch not in graphed and \
+                            self._graph_eligible(inter, n_sampled_items, verbose):
+                        step = graphed[batch] = _GraphedStep.capture(self, inter, uf, itf, n_sampled_items, learning_rate,
+                                                                     batched_alpha)
+                    self.last_step_form = "graph" if step else "eager"
+                    out = step.run(self, verbose) if step else self._train_step(inter, uf, itf, learning_rate, batched_alpha,
+                                                                                 n_sampled_items, want_stats=verbose)
+                loss, serial_predictions, wr_loss = out
                 if verbose:
                     mean_loss = float(loss.mean())
                     mean_pred = float(serial_predictions.mean())
@@ -749,31 +749,17 @@ class TensorRec(object):
         """Eager steps advance only the host counters; before a replay the device state is brought back in line."""
         if self._schedule_mirror == (self._opt_step, self._sample_step):
             return
-        b1p, b2p = np.float32(1.0), np.float32(1.0)
-        for _ in range(int(self._opt_step)):
-            b1p = np.float32(b1p * np.float32(ADAM_BETA1))
-            b2p = np.float32(b2p * np.float32(ADAM_BETA2))
         host = np.zeros(4, np.float32)
-        host[0], host[1] = b1p, b2p
+        host[0], host[1] = _beta_powers(self._opt_step)
         host.view(np.uint32)[3] = np.uint32(self._sample_step & 0xFFFFFFFF)
         self._schedule.copy_(torch.from_numpy(host))
         self._schedule_mirror = (self._opt_step, self._sample_step)
 
     def _graph_eligible(self, inter, n_sampled_items, verbose):
-        if not self.hip_graphs or self._dp_active() or self._capture is not None or getattr(self, 'deterministic', False):
-            return False
-        if self._shared_negatives():          # one row of samples per step: eager steps only (docs/sampled_losses.md)
-            return False
-        # only steps made of the library's own launches are captured: the built-in losses on built-in graphs.  User-defined
-        # torch graphs / losses may do anything (host syncs, allocations the capture cannot follow) -- capturing them would
-        # fail, warn and fall back on every fit call.
-        if type(self.loss_graph_factory) not in _GRAPH_CAPTURABLE_LOSSES or not self._is_engine_graph():
-            return False
-        if len(self._graph_pool_owner) >= MAX_GRAPHED_BATCHES:
-            return False
-        pairs = inter.nnz + inter.shape[0] * int(n_sampled_items or 0)
-        dense = self.loss_graph_factory.is_dense
-        return pairs <= 4_000_000 and (not dense or inter.shape[0] * inter.shape[1] <= 4_000_000)
+        return step_plan.graph_eligible(
+            self.hip_graphs, self._dp_active(), self._capture is not None, getattr(self, 'deterministic', False),
+            self._shared_negatives(), type(self.loss_graph_factory) in _GRAPH_CAPTURABLE_LOSSES, self._is_engine_graph(),
+            len(self._graph_pool_owner), inter.nnz, inter.shape[0], inter.shape[1], n_sampled_items, self.loss_graph_factory.is_dense)
 
     def _shared_negatives(self):
         """The loss graph asks for ONE row of samples per step, shared by every user (SampledSoftmaxLossGraph(shared_negatives=True))."""
@@ -808,46 +794,21 @@ class TensorRec(object):
             x_item = PairIndex.make(inter.x_item, inter.x_item32, interactions=inter)
 
             engine = self._is_engine_graph()
-            # built-in WMRB on dot / cosine scores: one fused pass per user (csrc/wmrb_fused.hip) instead of
-            # serial scores -> loss -> autograd; only the exact built-in classes qualify (subclasses may override)
-            # (rows in registers: dot scores, S + the longest row <= 256; otherwise -- S in the thousands, Euclidean scores --
-            # the tiled form of the same step, csrc/wmrb_tiled.hip)
-            fused = tiled = fused_softmax = shared_mfma = False
+            # a one-pass step kernel instead of serial scores -> loss -> autograd, where step_plan.kernel names one
             shared = self._shared_negatives()
-            if (engine and not multi and graph.engine_mode in (ops.MODE_DOT, ops.MODE_EUCLIDEAN)
-                    and type(loss_graph) in (WMRBLossGraph, BalancedWMRBLossGraph)
-                    and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
-                    and user_reprs[0].shape[1] == item_repr.shape[1]):
-                fused = graph.engine_mode == ops.MODE_DOT and \
-                    ops.wmrb_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
-                tiled = not fused and ops.wmrb_tiled_supported(n_sampled_items, inter, int(item_repr.shape[1]))
-            # the built-in sampled softmax on dot / cosine scores: the same one-pass step with its own loss phase
-            # (csrc/softmax_fused.hip); Euclidean scores, subclasses and uncovered shapes take the generic step below
-            elif (engine and not multi and graph.engine_mode == ops.MODE_DOT and type(loss_graph) is SampledSoftmaxLossGraph
-                    and n_sampled_items is not None and item_repr.dim() == 2 and user_reprs[0].dim() == 2
-                    and user_reprs[0].shape[1] == item_repr.shape[1]):
-                if not shared:
-                    fused_softmax = ops.softmax_fused_supported(n_sampled_items, inter, int(item_repr.shape[1]))
-                elif not loss_graph.remove_accidental_hits:
-                    # one shared row of samples: the [U, S] logits as MFMA tiles (csrc/softmax_shared.hip); hits removed, Euclidean
-                    # scores, subclasses and uncovered d expand the row and take the generic step below, never the per-user fused one
-                    shared_mfma = ops.softmax_shared_supported(n_sampled_items, inter, int(item_repr.shape[1]))
+            same_width = item_repr.dim() == 2 and user_repr.dim() == 2 and user_repr.shape[1] == item_repr.shape[1]
+            kernel = step_plan.kernel(step_plan.loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi, same_width,
+                                      n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]), shared,
+                                      getattr(loss_graph, 'remove_accidental_hits', False))
             u_ins, a_ins, i_in = user_reprs, attn_reprs, item_repr
             if engine and graph.engine_normalize:     # cosine: normalise once, share between all serial calls
                 u_ins = [ops.l2_normalize_rows(u) for u in user_reprs]
                 a_ins = [ops.l2_normalize_rows(a) for a in attn_reprs] if attn_reprs is not None else None
                 i_in = ops.l2_normalize_rows(item_repr)
             u_in = u_ins[0]
-            if fused or tiled:
-                return self._fused_wmrb_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
-                                             n_sampled_items, want_stats, samples, apply,
-                                             tiled_mode=graph.engine_mode if tiled else None)
-            if fused_softmax:
-                return self._fused_softmax_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
-                                                n_sampled_items, want_stats, samples, apply)
-            if shared_mfma:
-                return self._shared_softmax_step(inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
-                                                 n_sampled_items, want_stats, samples, apply)
+            if kernel is not None:
+                return self._one_pass_step(kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
+                                           n_sampled_items, want_stats, samples, apply)
             self.last_step_kernel = None
             if multi:
                 pred_serial = self._serial_multi(u_ins, a_ins, i_in, x_user, x_item, user_bias, item_bias)
@@ -927,56 +888,31 @@ class TensorRec(object):
             return basic_loss, pred_serial, weights, n_loss
         return self._apply_gradients(basic_loss, pred_serial, weights, n_loss, learning_rate, alpha, want_stats)
 
-    def _fused_wmrb_step(self, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
-                         want_stats, samples=None, apply=True, tiled_mode=None):
-        """The WMRB step with the user side in one kernel: loss values and d(sum loss)/d(representations, biases) come
-        from ops.wmrb_fused_step; autograd then only carries them through the representation graphs (K1 backward)."""
+    def _one_pass_step(self, kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
+                       want_stats, samples=None, apply=True):
+        """The step with the user side in the one-pass kernel ``kernel`` (step_plan.kernel): loss values and d(sum loss) /
+        d(representations, biases) come from ops.<kernel>_step, fed like the generic step -- the loss graph's options, log q from the
+        sampler when it has one; autograd then only carries them through the representation graphs (K1 backward)."""
         loss_graph = self.loss_graph_factory
         if samples is None:
             samples = self._draw_samples(inter, n_sampled_items)
-        ub = user_bias if self.biased else None
-        ib = item_bias if self.biased else None
-        self.last_step_kernel = "wmrb_tiled" if tiled_mode is not None else "wmrb_fused"
-        if tiled_mode is not None:
-            basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.wmrb_tiled_step(u_in, i_in, ub, ib, inter, samples,
-                                                                                balanced=loss_graph.balanced, mode=tiled_mode)
+        self.last_step_kernel = kernel
+        operands = (u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter)
+        if kernel == "wmrb_fused":
+            out = ops.wmrb_fused_step(*operands, samples, balanced=loss_graph.balanced)
+        elif kernel == "wmrb_tiled":
+            out = ops.wmrb_tiled_step(*operands, samples, balanced=loss_graph.balanced, mode=self.prediction_graph_factory.engine_mode)
         else:
-            basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.wmrb_fused_step(u_in, i_in, ub, ib, inter, samples,
-                                                                                balanced=loss_graph.balanced)
-        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
-                                       learning_rate, alpha, want_stats, apply)
-
-    def _fused_softmax_step(self, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
-                            want_stats, samples=None, apply=True):
-        """The sampled-softmax step with the user side in one kernel (ops.softmax_fused_step), fed like the generic step: the
-        loss graph's temperature and options, log q from the sampler when it has one."""
-        loss_graph = self.loss_graph_factory
-        if samples is None:
-            samples = self._draw_samples(inter, n_sampled_items)
-        self.last_step_kernel = "softmax_fused"
-        log_q = getattr(self.sampler, 'log_q', None)
-        basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.softmax_fused_step(
-            u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter, samples,
-            loss_graph.temperature, sample_log_q=log_q(self._store.device) if callable(log_q) else None,
-            log_q_correction=loss_graph.log_q_correction, remove_accidental_hits=loss_graph.remove_accidental_hits)
-        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
-                                       learning_rate, alpha, want_stats, apply)
-
-    def _shared_softmax_step(self, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha, n_sampled_items,
-                             want_stats, samples=None, apply=True):
-        """The sampled-softmax step with ONE row of samples for the whole batch (ops.softmax_shared_step): the loss graph's
-        temperature and logQ option, log q from the sampler when it has one."""
-        loss_graph = self.loss_graph_factory
-        if samples is None:
-            samples = self._draw_samples(inter, n_sampled_items)
-        self.last_step_kernel = "softmax_shared"
-        log_q = getattr(self.sampler, 'log_q', None)
-        basic_loss, pred_serial, d_u, d_v, d_ub, d_ib = ops.softmax_shared_step(
-            u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter, samples[0],
-            loss_graph.temperature, sample_log_q=log_q(self._store.device) if callable(log_q) else None,
-            log_q_correction=loss_graph.log_q_correction)
-        return self._finish_fused_step(basic_loss, pred_serial, (d_u, d_v, d_ub, d_ib), u_in, i_in, user_bias, item_bias, weights,
-                                       learning_rate, alpha, want_stats, apply)
+            log_q = getattr(self.sampler, 'log_q', None)
+            options = dict(sample_log_q=log_q(self._store.device) if callable(log_q) else None,
+                           log_q_correction=loss_graph.log_q_correction)
+            if kernel == "softmax_fused":
+                out = ops.softmax_fused_step(*operands, samples, loss_graph.temperature,
+                                             remove_accidental_hits=loss_graph.remove_accidental_hits, **options)
+            else:                           # "softmax_shared": the one row every user shares
+                out = ops.softmax_shared_step(*operands, samples[0], loss_graph.temperature, **options)
+        return self._finish_fused_step(out[0], out[1], out[2:], u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
+                                       want_stats, apply)
 
     def _finish_fused_step(self, basic_loss, pred_serial, grads4, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                            want_stats, apply):
@@ -1997,7 +1933,6 @@ class TensorRec(object):
 # they became streaming reductions, csrc/loss_dense.hip)
 _GRAPH_CAPTURABLE_LOSSES = (RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph, BalancedWMRBLossGraph, SeparationLossGraph,
                             SeparationDenseLossGraph, SampledSoftmaxLossGraph, BPRLossGraph)
-MAX_GRAPHED_BATCHES = 64        # graphs kept alive by one fit call; further batches run eagerly
 
 
 class _GraphedStep(object):
@@ -2084,34 +2019,27 @@ class _GraphedStep(object):
 class _CoopStep(object):
     """One training step of one user batch as ONE cooperative kernel (csrc/step_coop.hip; trec_fit_step_coop): models that fit on
     chip -- BASELINE.json configs[1], 943 x 1,682, d = 64 -- are bound by launches, not by memory (~25 graph-replayed launches = 0.68 ms
-    per epoch).  Covered: LinearRepresentation on identity user features, LinearRepresentation on any item features, DotProduct,
-    WMRB / BalancedWMRB, one taste, single process.  Everything else keeps the multi-launch / HIP-graph step."""
+    per epoch).  Which models it covers: step_plan.coop_covered; everything else keeps the multi-launch / HIP-graph step."""
 
     @classmethod
     def plan(cls, model, inter, uf, itf, n_sampled_items):
-        from .representation_graphs import LinearRepresentationGraph
-        N = ops.N
-        if N.load().trec_get_tuning(b"fit_step_coop", 1) == 0 or model._dp_active() or model._capture is not None or \
-                getattr(model, 'deterministic', False) or model._multi() or model.attention_graph_factory is not None:
-            return None
-        if type(model.user_repr_graph_factory) is not LinearRepresentationGraph or \
-                type(model.item_repr_graph_factory) is not LinearRepresentationGraph or \
-                type(model.prediction_graph_factory) is not DotProductPredictionGraph or \
-                type(model.loss_graph_factory) not in (WMRBLossGraph, BalancedWMRBLossGraph) or not n_sampled_items:
-            return None
-        if not getattr(uf, "is_identity", False) or uf.shape[0] != inter.shape[0] or int(n_sampled_items) > inter.shape[1]:
+        n_users, n_items = inter.shape
+        d = int(model.n_components)
+        if not step_plan.coop_covered(
+                model._dp_active(), model._capture is not None, getattr(model, 'deterministic', False), model._multi(),
+                model.attention_graph_factory is not None, type(model.user_repr_graph_factory) is LinearRepresentationGraph,
+                type(model.item_repr_graph_factory) is LinearRepresentationGraph,
+                type(model.prediction_graph_factory) is DotProductPredictionGraph,
+                step_plan.loss_kind(model.loss_graph_factory) in step_plan.WMRB_KINDS, getattr(uf, "is_identity", False), uf.shape[0],
+                n_users, n_items, d, n_sampled_items, inter.max_row_nnz):
             return None
         store = model._store
         names = ["linear_weights_user_0", "linear_weights_item"] + (["user_feature_biases", "item_feature_biases"] if model.biased else [])
         if set(store.variables) != set(names) or any(n not in model._adam for n in names):
             return None                                         # (the first eager step creates variables and Adam slots)
-        n_users, n_items = inter.shape
-        d = int(model.n_components)
         if store.variables[names[0]].shape != (n_users, d) or store.variables[names[1]].shape != (itf.shape[1], d):
             return None
-        need = int(N.query("trec_fit_step_coop_workspace_floats", n_users, n_items, d, int(n_sampled_items), int(inter.max_row_nnz)))
-        if need < 0:
-            return None
+        need = step_plan.coop_workspace_floats(n_users, n_items, d, n_sampled_items, inter.max_row_nnz)
         self = cls()
         self.inter, self.itf, self.S, self.names = inter, itf, int(n_sampled_items), names
         dev = store.device
@@ -2125,17 +2053,9 @@ class _CoopStep(object):
         return self
 
     def _lr_t(self, lr, t):
-        if self.powers is None or self.powers[0] != t - 1:
-            b1p, b2p = np.float32(1.0), np.float32(1.0)
-            for _ in range(int(t) - 1):
-                b1p = np.float32(b1p * np.float32(ADAM_BETA1))
-                b2p = np.float32(b2p * np.float32(ADAM_BETA2))
-        else:
-            _, b1p, b2p = self.powers
-        b1p = np.float32(b1p * np.float32(ADAM_BETA1))
-        b2p = np.float32(b2p * np.float32(ADAM_BETA2))
-        self.powers = (t, b1p, b2p)
-        return float(np.float32(np.float32(lr) * np.sqrt(np.float32(1.0) - b2p) / (np.float32(1.0) - b1p)))
+        start = self.powers if self.powers is not None and self.powers[0] == t - 1 else None      # (the previous step's: one product)
+        self.powers = (t,) + _beta_powers(t, start)
+        return _adam_lr_t(lr, t, self.powers[1:])
 
     def run(self, model, learning_rate, alpha, want_stats):
         """Returns (loss, serial predictions, weight-reg loss) like _train_step, or False when the device refused the launch (the
