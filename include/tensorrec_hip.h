@@ -705,6 +705,17 @@ int trec_softmax_shared_grads(const float* U, const float* Vs, const float* user
                               float* d_sample_bias, void* stream);
 int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int64_t* order, const float* dVs, const float* d_sample_bias,
                                 int32_t n_sampled, int32_t d, int64_t n_items, float* dV, float* d_item_bias, void* stream);
+/* The positives of the FULL softmax over the catalogue, loss_p = log sum_i exp((y_ui - y_up) inv_temperature), for the step that
+ * streams the item representation itself through _stats / _grads above (Vs = V, sample_bias = item_bias, sample_c = NULL, n_sampled =
+ * n_items; no scatter): with w = y inv_temperature, M[u] = max_i w_ui and Z[u] = sum_i exp(w_ui - M[u]) from _stats -- the positives
+ * are in the sums -- one thread per user writes, for every interaction with pos_slot >= 0,
+ *     loss[pos_slot] = (M[u] - pred_serial inv_temperature) + logf(Z[u]),   d_pred = -inv_temperature   (upstream gradient 1),
+ * d_pred = 0 and no loss for pos_slot < 0, tK[u] = inv_temperature n_u / Z[u] with n_u the user's count of pos_slot >= 0 (0 for a user
+ * without positives) -- _grads' P_ui = tK[u] exp(w_ui - M[u]) is then the softmax's share of d y_ui -- and d_user_bias (nullable) [u] =
+ * 0.f exactly: the loss is invariant under a shift of the row.  Nothing is clamped.  Errors as trec_softmax_shared_positives. */
+int trec_softmax_full_positives(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* M,
+                                const float* Z, int64_t n_users, float inv_temperature, float* loss, float* d_pred, float* tK,
+                                float* d_user_bias, void* stream);
 /* The same step for S in the thousands, long interaction rows and Euclidean scores (csrc/wmrb_tiled.hip): the user's S + n_u item
  * rows are streamed twice in tiles (scores into LDS, then the coefficient-weighted sum dU) instead of living in registers.
  * mode 0: dot scores (prediction_graphs.py:52-55; cosine = dot on normalised rows, :70-72); mode 1: euclidean,
@@ -764,6 +775,24 @@ int trec_dense_loss_fwd_phase(int32_t kind, int32_t phase, const float* pred, in
                               void* stream);
 int trec_dense_loss_bwd(int32_t kind, const float* pred, int64_t rows, int64_t cols, const int32_t* xu, const int32_t* xi,
                         const float* values, int64_t n_pairs, const double* st, const float* gl, float* d_pred, void* stream);
+/* The full softmax (multinomial likelihood) over every item of the catalogue on a real prediction tensor (csrc/loss_dense.hip;
+ * SoftmaxDenseLossGraph's generic form -- not in the reference).  pred [n_users, n_items] with row stride ld >= n_items; the
+ * interactions as CSR over users: indptr [n_users + 1], x_item sorted within a row (equal columns adjacent), pos_slot [nnz] the slot
+ * of the interaction in the compact [P+] vector or < 0 (not a positive: its item still counts in the denominator).  With t =
+ * inv_temperature, w_ui = pred_ui t, M_u = max_i w_ui, Z_u = sum_i exp(w_ui - M_u) (>= 1):
+ *     _fwd   row_max[u] = M_u, row_sum[u] = Z_u (one pass per row, online, a wave per row up to 512 items and a 256-thread workgroup
+ *            beyond; fixed-order reductions), loss[pos_slot] = (M_u - w_up) + logf(Z_u); a user without positives writes no loss.
+ *     _bwd   G_u = sum_p grad_loss[pos_slot_p] in interaction order;  d_pred_ui = (t G_u / Z_u) expf(w_ui - M_u) - t sum_{p of u on
+ *            item i} grad_loss_p, the positives subtracted in interaction order, duplicates each; d_pred [n_users, n_items]
+ *            contiguous, every entry written (a user without positives: a zero row).
+ * Magnitudes are ignored; nothing is clamped; no atomics: two calls are bit-identical.  Errors before any launch: TREC_ERR_INVALID
+ * for null pointers, n_items outside [1, 2^31), ld < n_items, an inv_temperature that is not finite and > 0. */
+int trec_softmax_dense_fwd(const float* pred, int64_t ld, const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                           int64_t n_users, int64_t n_items, float inv_temperature, float* loss, float* row_max, float* row_sum,
+                           void* stream);
+int trec_softmax_dense_bwd(const float* pred, int64_t ld, const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                           const float* row_max, const float* row_sum, const float* grad_loss, int64_t n_users, int64_t n_items,
+                           float inv_temperature, float* d_pred, void* stream);
 /* The dense losses WITHOUT the [n_users, n_items] prediction (csrc/loss_dense.hip, "factored"): dot-product scores are bilinear,
  * p_ui = x_u . y_i with x_u = [u | b_u | 1], y_i = [v_i | 1 | b_i], so RMSEDense / SeparationDense (loss_graphs.py:62-72, :100-134)
  * need sum p = (sum x) . (sum y) and sum p^2 = <X^T X, Y^T Y>_F only, and their gradient is A X (Y^T Y) + B 1 (sum y)^T.

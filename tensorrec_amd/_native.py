@@ -157,6 +157,7 @@ SIGNATURES = {
     "trec_softmax_shared_positives": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp],
     "trec_softmax_shared_grads": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f, _i32, _vp, _vp, _vp, _vp, _vp],
     "trec_softmax_shared_scatter": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp],
+    "trec_softmax_full_positives": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp],
     "trec_wmrb_tiled_lds_bytes": [_i32, _i32, _i32],
     "trec_wmrb_tiled_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
@@ -167,6 +168,8 @@ SIGNATURES = {
     "trec_dense_loss_fwd": [_i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "trec_dense_loss_fwd_phase": [_i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "trec_dense_loss_bwd": [_i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "trec_softmax_dense_fwd": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _f, _vp, _vp, _vp, _vp],
+    "trec_softmax_dense_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f, _vp, _vp],
     "trec_gram_f64": [_vp, _i64, _i32, _i64, _vp, _vp],
     "trec_dense_loss_factored_phase": [_i32, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "trec_dense_loss_factored_bwd": [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],

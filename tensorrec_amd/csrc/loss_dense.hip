@@ -271,6 +271,141 @@ __global__ __launch_bounds__(256) void factored_bwd_kernel(int kind, const float
     else d_serial[p] = (y[p] > 0.f) ? sep_grad((double)serial[p], true, st, np, nn, g) - sep_grad((double)serial[p], false, st, np, nn, g) : 0.f;
 }
 
+// ---- the full softmax over every item of the catalogue on a real [n_users, n_items] prediction (SoftmaxDenseLossGraph, generic form)
+// t = 1 / temperature, w_ui = y_ui t, M_u = max_i w_ui, Z_u = sum_i exp(w_ui - M_u) (>= 1):
+//     loss_p = (M_u - w_up) + log Z_u          d y_ui = (t G_u / Z_u) exp(w_ui - M_u) - t sum_{p of u on item i} go_p,   G_u = sum_p go_p
+// One row per wave (T = 64, short rows) or per 256-thread workgroup (T = 256).  A thread keeps an online (m, z) over its strided
+// elements, four at a time: the running sum is rescaled by exp(m_old - m_new) when the maximum moves.  The threads' pairs are merged
+// by xor butterflies (both partners form the same sum: the addition commutes), the four waves' in wave order: a fixed order, no
+// atomics, nothing clamped.  w is rounded ONCE (sd_w keeps the product out of a contraction with the subtraction that follows) so
+// that the maximum, the exponentials and the loss all see the same float.
+#define SD_WAVE_MAX_ITEMS 512      // rows up to this length take the wave-per-row form
+
+__device__ __forceinline__ float sd_w(float y, float t)
+{
+    float w = y * t;
+    asm volatile("" : "+v"(w));
+    return w;
+}
+
+__device__ __forceinline__ void sd_merge(float& m, float& z, float om, float oz)
+{
+    const float mx = fmaxf(m, om);
+    const float a = (m > -INFINITY) ? z * expf(m - mx) : 0.f;         // (a side that saw no element adds an exact 0)
+    const float b = (om > -INFINITY) ? oz * expf(om - mx) : 0.f;
+    m = mx;
+    z = a + b;
+}
+
+// (M, Z) of one row in every thread of the T that own it; r = the thread's index among them; red: 8 floats of LDS (T = 256)
+template <int T>
+__device__ __forceinline__ void sd_row_stats(const float* __restrict__ row, int64_t n, float t, int r, float* red, float& m, float& z)
+{
+    m = -INFINITY;
+    z = 0.f;
+    for (int64_t i0 = r; i0 < n; i0 += 4 * T) {
+        float w[4];
+        float cm = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = i0 + (int64_t)e * T;
+            w[e] = (i < n) ? sd_w(row[i], t) : -INFINITY;
+            cm = fmaxf(cm, w[e]);
+        }
+        if (cm > m) {
+            z = z * expf(m - cm);                                      // (first chunk: 0 * exp(-inf) = 0)
+            m = cm;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z += expf(w[e] - m);               // (past the row: exp(-inf) = 0)
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const float om = __shfl_xor(m, off, 64), oz = __shfl_xor(z, off, 64);
+        sd_merge(m, z, om, oz);
+    }
+    if (T == 256) {
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = m; red[4 + (threadIdx.x >> 6)] = z; }
+        __syncthreads();
+        m = red[0];
+        z = red[4];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) sd_merge(m, z, red[k], red[4 + k]);
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void softmax_dense_fwd_kernel(const float* __restrict__ pred, int64_t ld, const int64_t* __restrict__ indptr,
+                                                               const int32_t* __restrict__ x_item, const int32_t* __restrict__ pos_slot,
+                                                               int64_t n_users, int64_t n_items, float t, float* __restrict__ loss,
+                                                               float* __restrict__ Mu, float* __restrict__ Zu)
+{
+    __shared__ float red[8];
+    const int r = (T == 64) ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    const int64_t u = (T == 64) ? (((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6) : (int64_t)blockIdx.x;
+    if (u >= n_users) return;                                          // (uniform per wave / per workgroup)
+    const float* row = pred + u * ld;
+    float m, z;
+    sd_row_stats<T>(row, n_items, t, r, red, m, z);
+    if (r == 0) { Mu[u] = m; Zu[u] = z; }
+    const float lz = logf(z);
+    const int64_t b = indptr[u], e = indptr[u + 1];
+    for (int64_t p = b + r; p < e; p += T) {
+        const int32_t slot = pos_slot[p];
+        const int32_t i = x_item[p];
+        if (slot < 0 || (uint32_t)i >= (uint64_t)n_items) continue;
+        loss[slot] = (m - sd_w(row[i], t)) + lz;
+    }
+}
+
+// one streaming pass writes (t G / Z) exp(w - M); then the owner of each run of equal columns (rows are sorted by column: equal columns
+// are adjacent) subtracts t go_p of the run's positives in interaction order -- duplicates each, one owner per cell, no atomics
+template <int T>
+__global__ __launch_bounds__(256) void softmax_dense_bwd_kernel(const float* __restrict__ pred, int64_t ld, const int64_t* __restrict__ indptr,
+                                                               const int32_t* __restrict__ x_item, const int32_t* __restrict__ pos_slot,
+                                                               const float* __restrict__ Mu, const float* __restrict__ Zu,
+                                                               const float* __restrict__ go, int64_t n_users, int64_t n_items, float t,
+                                                               float* __restrict__ d_pred)
+{
+    const int r = (T == 64) ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    const int64_t u = (T == 64) ? (((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6) : (int64_t)blockIdx.x;
+    const bool live = u < n_users;
+    const int64_t b = live ? indptr[u] : 0, e = live ? indptr[u + 1] : 0;
+    float* drow = d_pred + (live ? u : 0) * n_items;
+    if (live) {
+        float G = 0.f;                                                 // every thread adds the row's go in interaction order
+        for (int64_t p = b; p < e; ++p) {
+            const int32_t slot = pos_slot[p];
+            if (slot >= 0 && (uint32_t)x_item[p] < (uint64_t)n_items) G += go[slot];
+        }
+        const float M = Mu[u];
+        const float coef = (t * G) / Zu[u];
+        const float* row = pred + u * ld;
+        for (int64_t i0 = r; i0 < n_items; i0 += 4 * T) {
+            float y[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int64_t i = i0 + (int64_t)k * T; y[k] = row[i < n_items ? i : i0]; }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = i0 + (int64_t)k * T;
+                if (i < n_items) drow[i] = coef * expf(sd_w(y[k], t) - M);
+            }
+        }
+    }
+    __syncthreads();                                                   // the row's writes are visible to its owners below
+    for (int64_t p = b + r; p < e; p += T) {
+        const int32_t i = x_item[p];
+        if ((uint32_t)i >= (uint64_t)n_items || (p > b && x_item[p - 1] == i)) continue;
+        float acc = drow[i];
+        bool any = false;
+        for (int64_t q = p; q < e && x_item[q] == i; ++q) {
+            const int32_t slot = pos_slot[q];
+            if (slot >= 0) { acc -= t * go[slot]; any = true; }
+        }
+        if (any) drow[i] = acc;
+    }
+}
+
 unsigned grid_for(int64_t n, int per_thread)
 {
     int64_t b = ceil_div64(n, 256 * (int64_t)per_thread);
@@ -415,4 +550,46 @@ extern "C" int trec_dense_loss_factored_bwd(int32_t kind, const float* pred_seri
     hipLaunchKernelGGL(factored_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (int)kind, pred_serial, values,
                        n_pairs, st, gl, d_serial, coef);
     return trec_check_launch("trec_dense_loss_factored_bwd");
+}
+
+// The full softmax over the catalogue on a dense prediction (SoftmaxDenseLossGraph, generic form; formulas above the kernels).
+// pred [n_users, n_items] with row stride ld >= n_items; the interactions as CSR over users (indptr, x_item sorted within a row,
+// pos_slot < 0: not a positive); loss [P+], row_max / row_sum [n_users] kept for the backward pass.
+static bool sd_temperature_ok(float inv_temperature) { return inv_temperature > 0.f && inv_temperature <= 3.402823466e+38f; }
+
+extern "C" int trec_softmax_dense_fwd(const float* pred, int64_t ld, const int64_t* indptr, const int32_t* x_item,
+                                      const int32_t* pos_slot, int64_t n_users, int64_t n_items, float inv_temperature, float* loss,
+                                      float* row_max, float* row_sum, void* stream)
+{
+    TREC_REQUIRE(pred && indptr && x_item && pos_slot && loss && row_max && row_sum, "trec_softmax_dense_fwd: null pointer");
+    TREC_REQUIRE(n_items >= 1 && n_items < ((int64_t)1 << 31) && ld >= n_items, "trec_softmax_dense_fwd: need 1 <= n_items < 2^31 and ld >= n_items");
+    TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_dense_fwd: n_users must lie in [0, 2^31)");
+    TREC_REQUIRE(sd_temperature_ok(inv_temperature), "trec_softmax_dense_fwd: inv_temperature must be finite and > 0");
+    if (n_users == 0) return TREC_OK;
+    if (n_items <= SD_WAVE_MAX_ITEMS)
+        hipLaunchKernelGGL(softmax_dense_fwd_kernel<64>, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           pred, ld, indptr, x_item, pos_slot, n_users, n_items, inv_temperature, loss, row_max, row_sum);
+    else
+        hipLaunchKernelGGL(softmax_dense_fwd_kernel<256>, dim3((unsigned)n_users), dim3(256), 0, (hipStream_t)stream, pred, ld, indptr,
+                           x_item, pos_slot, n_users, n_items, inv_temperature, loss, row_max, row_sum);
+    return trec_check_launch("trec_softmax_dense_fwd");
+}
+
+// d_pred [n_users, n_items] contiguous, every entry written; grad_loss [P+] the upstream gradient
+extern "C" int trec_softmax_dense_bwd(const float* pred, int64_t ld, const int64_t* indptr, const int32_t* x_item,
+                                      const int32_t* pos_slot, const float* row_max, const float* row_sum, const float* grad_loss,
+                                      int64_t n_users, int64_t n_items, float inv_temperature, float* d_pred, void* stream)
+{
+    TREC_REQUIRE(pred && indptr && x_item && pos_slot && row_max && row_sum && grad_loss && d_pred, "trec_softmax_dense_bwd: null pointer");
+    TREC_REQUIRE(n_items >= 1 && n_items < ((int64_t)1 << 31) && ld >= n_items, "trec_softmax_dense_bwd: need 1 <= n_items < 2^31 and ld >= n_items");
+    TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_dense_bwd: n_users must lie in [0, 2^31)");
+    TREC_REQUIRE(sd_temperature_ok(inv_temperature), "trec_softmax_dense_bwd: inv_temperature must be finite and > 0");
+    if (n_users == 0) return TREC_OK;
+    if (n_items <= SD_WAVE_MAX_ITEMS)
+        hipLaunchKernelGGL(softmax_dense_bwd_kernel<64>, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                           pred, ld, indptr, x_item, pos_slot, row_max, row_sum, grad_loss, n_users, n_items, inv_temperature, d_pred);
+    else
+        hipLaunchKernelGGL(softmax_dense_bwd_kernel<256>, dim3((unsigned)n_users), dim3(256), 0, (hipStream_t)stream, pred, ld, indptr,
+                           x_item, pos_slot, row_max, row_sum, grad_loss, n_users, n_items, inv_temperature, d_pred);
+    return trec_check_launch("trec_softmax_dense_bwd");
 }

@@ -293,6 +293,34 @@ __global__ __launch_bounds__(256) void shared_positives_kernel(const int64_t* __
     if (d_user_bias) d_user_bias[u] = sdy + tk * Zu;
 }
 
+// The FULL softmax (the streamed matrix is the item representation itself, S = n_items): the positives are in the denominator, so
+// (M_u, Z_u) already cover them.  One thread per user: loss_p = (M_u - w_p) + log Z_u with w_p = K3's score times t, d y_p = -t,
+// tK_u = t n_u / Z_u with n_u the user's interactions of pos_slot >= 0 (upstream gradient 1: G_u = n_u).  The loss does not move
+// when the row is shifted: d b_u is an exact 0.
+__global__ __launch_bounds__(256) void full_positives_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot,
+                                                             const float* __restrict__ pred, const float* __restrict__ M,
+                                                             const float* __restrict__ Z, int64_t n_users, float inv_t,
+                                                             float* __restrict__ loss, float* __restrict__ d_pred,
+                                                             float* __restrict__ tK, float* __restrict__ d_user_bias)
+{
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= n_users) return;
+    const int64_t b = indptr[u], e = indptr[u + 1];
+    const float Mu = M[u], Zu = Z[u];
+    const float lz = logf(Zu);
+    int n = 0;
+    for (int64_t q = b; q < e; ++q) {
+        const int32_t slot = pos_slot[q];
+        if (slot < 0) { d_pred[q] = 0.f; continue; }
+        const float wp = pred[q] * inv_t;
+        loss[slot] = (Mu - wp) + lz;
+        d_pred[q] = -inv_t;
+        ++n;
+    }
+    tK[u] = n ? (inv_t * (float)n) / Zu : 0.f;
+    if (d_user_bias) d_user_bias[u] = 0.f;
+}
+
 // dV[id] += the rows of equal ids in slot order (ids sorted stably: `order` is the slot of sorted position j); one owner per id
 __global__ __launch_bounds__(256) void shared_scatter_kernel(const int32_t* __restrict__ sorted_ids, const int64_t* __restrict__ order,
                                                              const float* __restrict__ dVs, const float* __restrict__ dbs, int S, int d,
@@ -432,4 +460,19 @@ extern "C" int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int6
     hipLaunchKernelGGL(shared_scatter_kernel, dim3((unsigned)ceil_div64((int64_t)n_sampled * (d + 1), 256)), dim3(256), 0,
                        (hipStream_t)stream, sorted_ids, order, dVs, d_sample_bias, n_sampled, d, n_items, dV, d_item_bias);
     return trec_check_launch("trec_softmax_shared_scatter");
+}
+
+// the positives of the full softmax (full_positives_kernel): pred_serial = K3's scores of the interactions, (M, Z) = _stats' answer
+// with Vs = the whole item representation
+extern "C" int trec_softmax_full_positives(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* M,
+                                           const float* Z, int64_t n_users, float inv_temperature, float* loss, float* d_pred,
+                                           float* tK, float* d_user_bias, void* stream)
+{
+    TREC_REQUIRE(indptr && M && Z && tK, "trec_softmax_full_positives: null pointer");
+    TREC_REQUIRE(ss_temperature_ok(inv_temperature), "trec_softmax_full_positives: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(n_users >= 0, "trec_softmax_full_positives: n_users must be >= 0");
+    if (n_users == 0) return TREC_OK;
+    hipLaunchKernelGGL(full_positives_kernel, dim3((unsigned)ceil_div64(n_users, 256)), dim3(256), 0, (hipStream_t)stream, indptr,
+                       pos_slot, pred_serial, M, Z, n_users, inv_temperature, loss, d_pred, tK, d_user_bias);
+    return trec_check_launch("trec_softmax_full_positives");
 }

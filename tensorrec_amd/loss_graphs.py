@@ -157,6 +157,33 @@ class SampledSoftmaxLossGraph(AbstractLossGraph):
                                         remove_accidental_hits=self.remove_accidental_hits)
 
 
+class SoftmaxDenseLossGraph(AbstractLossGraph):
+    """
+    Full softmax (multinomial likelihood) over EVERY item of the catalogue; not in the reference.  For every POSITIVE interaction
+    p = (u, i):
+        loss_p = log sum_j exp((yhat[u, j] - yhat_p) / temperature)
+    the loss the sampled softmax estimates (Mult-DAE / Mult-VAE, full-softmax two-tower models).  Magnitudes are ignored; an
+    interaction of value <= 0 is not a positive, but its item counts in the sum like any other; duplicate (u, i) entries are each
+    their own positive.  Returns the [n_positive_interactions] vector.  On dot / cosine scores with an embedding width the tile
+    kernel covers, the step never forms the [n_users, n_items] predictions (csrc/softmax_shared.hip streams the item representation
+    as MFMA tiles: step_plan.dense_kernel); every other prediction graph hands its dense predictions to csrc/loss_dense.hip.
+    docs/sampled_losses.md, "Full softmax".
+    """
+    is_dense = True
+
+    def __init__(self, temperature=1.0):
+        try:
+            temperature = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+        if not (temperature > 0.0 and temperature != float("inf")):
+            raise ValueError("temperature must be a finite float > 0, got %r" % (temperature,))
+        self.temperature = temperature
+
+    def connect_loss_graph(self, tf_prediction, tf_interactions, **kwargs):
+        return ops.softmax_dense_loss(tf_prediction, tf_interactions, temperature=self.temperature)
+
+
 class BPRLossGraph(AbstractLossGraph):
     """
     Bayesian personalised ranking, the pairwise logistic loss; not in the reference.  For every POSITIVE interaction p = (u, i):

@@ -867,8 +867,10 @@ GROUP_BINNED_MIN_PAIRS = int(_os.environ.get("TREC_BINNED_MIN_PAIRS", 1 << 22)) 
 
 
 def step_switch(name):
-    """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT.)"""
-    return N.load().trec_get_tuning(name.encode(), SOFTMAX_SHARED_DEFAULT if name == "softmax_shared" else 1) != 0
+    """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT,
+    "softmax_full" to SOFTMAX_FULL_DEFAULT.)"""
+    default = SOFTMAX_SHARED_DEFAULT if name == "softmax_shared" else SOFTMAX_FULL_DEFAULT if name == "softmax_full" else 1
+    return N.load().trec_get_tuning(name.encode(), default) != 0
 
 
 def step_covers(kernel, n_sampled, max_row_nnz, d):
@@ -1125,6 +1127,68 @@ def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, sa
     sorted_ids, order = torch.sort(samples, stable=True)
     N.call("trec_softmax_shared_scatter", N.ptr(sorted_ids.contiguous()), N.ptr(order.contiguous()), N.ptr(d_vs), N.ptr(d_bs), S, d,
            n_items, N.ptr(d_v), N.ptr(d_ib))
+    return loss, pred, d_u, d_v, d_ub, d_ib
+
+
+SOFTMAX_FULL_DEFAULT = 0         # tuning "softmax_full" when nobody set it (docs/sampled_losses.md, "Full softmax": the measurement)
+
+
+def softmax_full_step(user_in, item_in, user_bias, item_bias, interactions, temperature):
+    """One step of the FULL softmax over the catalogue (SoftmaxDenseLossGraph) for dot scores on (user_in, item_in), upstream gradient
+    1: softmax_shared_step with the item representation itself as the streamed matrix (Vs = item_in, bs = item_bias, no constants,
+    S = n_items) -- no gather, no sort, no scatter, and the positives are in the denominator.  Returns (loss [P+], pred_serial [P],
+    d user_in, d item_in, d user_bias, d item_bias); d user_bias is an exact 0.  Nothing of size [n_users, n_items] exists and nothing
+    is read on the host."""
+    temperature = _checked_temperature(temperature)
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
+    n_users, n_items = interactions.shape
+    if u.dim() != 2 or v.dim() != 2 or u.shape[0] != n_users or v.shape[0] != n_items or u.shape[1] != v.shape[1] or n_users < 1:
+        raise ValueError("softmax_full_step needs [n_users, d] and [n_items, d] representations of the interactions' shape")
+    d, dev, nnz = int(u.shape[1]), u.device, interactions.nnz
+    if not step_covers("softmax_shared", n_items, 0, d):
+        raise ValueError("softmax_full_step covers d %% 4 == 0, 4 <= d <= %d; got d = %d" % (SOFTMAX_SHARED_MAX_D, d))
+    inv_t = 1.0 / temperature
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    with _timed("softmax_full_stats"):
+        N.call("trec_softmax_shared_stats", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), None, n_users, n_items, d, inv_t,
+               N.ptr(stat_m), N.ptr(stat_z))
+    if nnz:
+        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
+               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
+    N.call("trec_softmax_full_positives", N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
+           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
+    # The tile kernel's DU role ADDS to d user_in and its DV role OVERWRITES d item_in / d item_bias.  So the positives' K1 gather
+    # over the users runs BEFORE the tiles (it writes d_u, the tiles add the softmax's share onto it) and their K1 gather over the
+    # items runs AFTER them, accumulating (it adds -t u_u per positive, and -t per positive through the row-sum epilogue, onto what
+    # the tiles wrote): no buffer is zeroed, every cell has one writer at a time, the order of every sum is fixed.
+    if nnz:
+        if interactions.max_row_nnz > SPLIT_T:
+            d_u = spmm_split(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
+        else:
+            d_u = spmm_raw(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
+    else:
+        d_u = torch.zeros_like(u)
+    d_v = torch.empty_like(v)
+    d_ib = torch.empty((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
+    n_slices = int(N.query("trec_softmax_shared_slices", n_users, n_items, d))
+    ws = torch.empty((n_slices * n_items * (d + 1),), dtype=torch.float32, device=dev) if n_slices > 1 else None
+    with _timed("softmax_full_grads"):
+        N.call("trec_softmax_shared_grads", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), None, N.ptr(stat_m), N.ptr(t_k), n_users,
+               n_items, d, inv_t, n_slices, N.ptr(ws), N.ptr(d_u), N.ptr(d_v), N.ptr(d_ib))
+    if nnz:
+        indptr_t, users_t, perm_t = interactions.transposed()
+        if interactions.max_col_nnz > SPLIT_T:
+            spmm_split(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, accumulate=True, out=d_v,
+                       want_rowsum=d_ib if ib is not None else False)
+        else:
+            _spmm_rowsum(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, EPI_ROWSUM if ib is not None else EPI_NONE, True, d_v,
+                         d_ib)
     return loss, pred, d_u, d_v, d_ub, d_ib
 
 
@@ -1483,6 +1547,62 @@ def rmse_dense_loss(prediction, interactions):
     if isinstance(prediction, FactoredPrediction):
         return factored_dense_loss(prediction, interactions, DENSE_LOSS_RMSE_DENSE)
     return _DenseLoss.apply(prediction, DENSE_LOSS_RMSE_DENSE, interactions.x_user32, interactions.x_item32, interactions.values)
+
+
+def _row_strided(pred, n_items):
+    """(tensor, row stride) of a float32 [n_users, n_items] prediction whose rows are contiguous -- a view of a wider tensor is passed
+    as it is, its stride honoured by the kernels -- or a contiguous copy of anything else"""
+    if pred.dtype != torch.float32:
+        pred = pred.float()
+    if n_items > 1 and pred.stride(1) == 1 and pred.stride(0) >= n_items:
+        return pred, int(pred.stride(0))
+    return pred.contiguous(), n_items
+
+
+def _ptr_rows(t):
+    """device pointer of a tensor whose rows are contiguous (_row_strided); the checks of N.ptr but for the row stride"""
+    if not t.is_cuda or t.device.index != torch.cuda.current_device():
+        raise N.NativeLibraryError("expected a tensor on the current GPU, got device=%s" % t.device)
+    import ctypes
+    return ctypes.c_void_p(t.data_ptr())
+
+
+class _SoftmaxDense(torch.autograd.Function):
+    """trec_softmax_dense_fwd / _bwd (csrc/loss_dense.hip): the full softmax over the catalogue on a real [n_users, n_items]
+    prediction; the row statistics (M, Z) are kept for the backward pass, which writes the dense gradient in one streaming pass."""
+
+    @staticmethod
+    def forward(ctx, pred, inter: Interactions, inv_temperature):
+        n_users, n_items = inter.shape
+        if pred.dim() != 2 or tuple(pred.shape) != (n_users, n_items):
+            raise ValueError("tf_prediction has shape %s, the interactions %s" % (tuple(pred.shape), (n_users, n_items)))
+        pred, ld = _row_strided(pred, n_items)
+        dev = pred.device
+        loss = torch.empty((max(1, inter.n_positive),), dtype=torch.float32, device=dev)[:inter.n_positive]     # (never a null pointer)
+        row_max = torch.empty((n_users,), dtype=torch.float32, device=dev)
+        row_sum = torch.empty_like(row_max)
+        N.call("trec_softmax_dense_fwd", _ptr_rows(pred), ld, N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot),
+               n_users, n_items, inv_temperature, N.ptr(loss), N.ptr(row_max), N.ptr(row_sum))
+        ctx.inter, ctx.inv_temperature, ctx.ld = inter, inv_temperature, ld
+        ctx.save_for_backward(pred, row_max, row_sum)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        pred, row_max, row_sum = ctx.saved_tensors
+        inter = ctx.inter
+        n_users, n_items = inter.shape
+        d_pred = torch.empty((n_users, n_items), dtype=torch.float32, device=pred.device)
+        N.call("trec_softmax_dense_bwd", _ptr_rows(pred), ctx.ld, N.ptr(inter.indptr), N.ptr(inter.x_item32), N.ptr(inter.pos_slot),
+               N.ptr(row_max), N.ptr(row_sum), N.ptr(_f32c(gl) if gl.numel() else gl.new_zeros((1,))), n_users, n_items, ctx.inv_temperature, N.ptr(d_pred))
+        return d_pred, None, None
+
+
+def softmax_dense_loss(prediction, interactions, temperature=1.0):
+    """SoftmaxDenseLossGraph's generic form: the [n_positive] vector log sum_i exp((y_ui - y_up) / temperature) over EVERY item of the
+    catalogue, on a real [n_users, n_items] prediction (any prediction graph).  Magnitudes are ignored; an interaction of value <= 0
+    is not a positive, its item still counts in the sum; nothing is clamped."""
+    return _SoftmaxDense.apply(prediction, interactions, 1.0 / _checked_temperature(temperature))
 
 
 

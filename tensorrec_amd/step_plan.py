@@ -8,7 +8,7 @@ _CoopStep.plan and TensorRec._graph_eligible gather the inputs; the shapes a ker
 from collections import namedtuple
 
 from . import ops
-from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph
+from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph, SoftmaxDenseLossGraph
 
 Switches = namedtuple("Switches", "wmrb_fused wmrb_tiled softmax_fused softmax_shared fit_step_coop")
 # only the exact built-in classes have a kind: a subclass may override anything the kernels restate
@@ -55,6 +55,26 @@ def kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz,
             return "softmax_fused" if covered("softmax_fused") else None
         return "softmax_shared" if not remove_accidental_hits and covered("softmax_shared") else None
     return None
+
+
+def dense_loss_kind(loss_graph):
+    """"softmax_dense" for an instance of exactly SoftmaxDenseLossGraph, None for everything else (a subclass may override anything
+    the kernels restate).  Apart from ``kernel``'s table: a dense loss has no n_sampled and no entry in LOSS_KINDS."""
+    return "softmax_dense" if type(loss_graph) is SoftmaxDenseLossGraph else None
+
+
+def dense_kernel(loss, engine, engine_mode, multi, same_width, n_items, d, switch=None):
+    """The one-pass kernel of a training step under a DENSE loss -- "softmax_full": the full softmax with the item representation
+    streamed as MFMA tiles (csrc/softmax_shared.hip, ops.softmax_full_step) -- or None: the dense path (dense predictions -> loss graph
+    -> autograd).  ``loss``: dense_loss_kind's answer; ``engine`` / ``engine_mode``: the prediction graph is a built-in one, and its
+    mode (cosine counts as dot: the step is fed the normalised operands); ``multi``: several tastes; ``same_width``: both
+    representations are 2-D and equally wide, ``d`` that width; ``switch``: tuning "softmax_full", None reads the library's."""
+    if loss != "softmax_dense" or not engine or engine_mode != ops.MODE_DOT or multi or not same_width:
+        return None
+    if not ops.step_covers("softmax_shared", n_items, 0, d):
+        return None
+    on = ops.step_switch("softmax_full") if switch is None else switch
+    return "softmax_full" if on else None
 
 
 def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,

@@ -39,7 +39,7 @@ from .errors import (
 from .framework import VariableStore, variable_scope, resolve_device
 from .loss_graphs import (AbstractLossGraph, RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph,
                           BalancedWMRBLossGraph, SeparationLossGraph, SeparationDenseLossGraph, SampledSoftmaxLossGraph,
-                          BPRLossGraph)
+                          BPRLossGraph, SoftmaxDenseLossGraph)
 from .prediction_graphs import AbstractPredictionGraph, DotProductPredictionGraph
 from .recommendation_graphs import (
     project_biases, bias_prediction_dense, bias_prediction_serial, rank_predictions,
@@ -379,7 +379,7 @@ class TensorRec(object):
         self._graph_pool_owner = []
         self.last_route = None        # what predict_top_k did last (route report)
         self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused",
-                                      # "softmax_shared";
+                                      # "softmax_shared", "softmax_full" (step_plan.dense_kernel);
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -809,6 +809,15 @@ class TensorRec(object):
             if kernel is not None:
                 return self._one_pass_step(kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                            n_sampled_items, want_stats, samples, apply)
+            # the full softmax on dot / cosine scores: the item representation streamed as MFMA tiles, no [n_users, n_items] tensor
+            dense = step_plan.dense_kernel(step_plan.dense_loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi,
+                                           same_width, n_items, int(item_repr.shape[-1]))
+            if dense == "softmax_full":
+                self.last_step_kernel = dense
+                out = ops.softmax_full_step(u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None,
+                                            inter, loss_graph.temperature)
+                return self._finish_fused_step(out[0], out[1], out[2:], u_in, i_in, user_bias, item_bias, weights, learning_rate,
+                                               alpha, want_stats, apply)
             self.last_step_kernel = None
             if multi:
                 pred_serial = self._serial_multi(u_ins, a_ins, i_in, x_user, x_item, user_bias, item_bias)
