@@ -633,6 +633,27 @@ int trec_bpr_adj_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t
 int trec_bpr_adj_bwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
                      const float* sample_pred, const int32_t* samples, const float* grad_loss, int64_t n_users, int32_t n_sampled,
                      int32_t remove_hits, float* d_pred_serial, float* d_sample_pred, void* stream);
+/* WARP (Weston et al., "WSABIE"; csrc/loss_warp.hip).  This replaces no TF op chain -- the reference has no such loss -- the
+ * formulas are the definition.  Layout and conventions of trec_bpr_fwd / _bwd and of the hit-removing pairs above: indptr, pos_slot
+ * (-1: the interaction is no positive, its d_pred_serial is 0), pred_serial [n_interactions], sample_pred [n_users, n_sampled],
+ * loss [n_positive]; a user without positives writes no loss and gets a zero d_sample_pred row; no atomics, every sum in a fixed order.
+ * A wave per user for n_sampled <= 256 (tuning wmrb_wave, as for WMRB), a workgroup per user up to 16384.
+ *   A user's samples are tried in table order.  v_s = (1.0f - y_p) + y_s in float32, in this order; sample s violates iff v_s > 0
+ *   (strictly).  Sample s is kept unless remove_hits is set and its item (samples) is the column (x_item) of an interaction of the
+ *   user with pos_slot >= 0; the mask is per user.  f_p = the smallest kept s that violates, N_p = the number of kept samples with
+ *   index <= f_p (f_p + 1 without remove_hits), r_p = (n_items - 1) div N_p, L_p = logf((float)max(r_p, 1)), loss_p = L_p v_{f_p}.
+ *   No kept violator: loss_p = 0, f_p = -1, L_p = 0.  L is not differentiated:  d y_p = -go_p L_p,
+ *   d y_us = sum_{p of u, f_p = s} go_p L_p, summed in interaction order.
+ *   first (int32) and weight (float32), both [n_interactions]: f_p and L_p, written by the forward pass for the backward pass, which
+ *   reads no prediction; an interaction with pos_slot < 0 gets first = -1 and weight = 0.
+ * x_item and samples may be NULL unless remove_hits.  TREC_ERR_INVALID before any launch for a null required pointer, n_sampled
+ * outside [1, 16384], n_items outside [1, 2^31), null samples or x_item with remove_hits.                                        */
+int trec_warp_fwd(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const float* pred_serial,
+                  const float* sample_pred, const int32_t* samples, int64_t n_users, int64_t n_items, int32_t n_sampled,
+                  int32_t remove_hits, float* loss, int32_t* first, float* weight, void* stream);
+int trec_warp_bwd(const int64_t* indptr, const int32_t* pos_slot, const int32_t* first, const float* weight,
+                  const float* grad_loss, int64_t n_users, int32_t n_sampled, float* d_pred_serial, float* d_sample_pred,
+                  void* stream);
 /* One WMRB training step's user side in one pass (csrc/wmrb_fused.hip): serial + sample predictions
  * (prediction_graphs.py:52-55 + recommendation_graphs.py:55-57 over tensorrec.py:384-395), the WMRB / BalancedWMRB loss
  * (loss_graphs.py:153-227) and, for the SUM of the loss vector (what tensorrec.py:487-489 minimises), its gradient

@@ -206,3 +206,31 @@ class BPRLossGraph(AbstractLossGraph):
             return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions)
         return ops.bpr_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions, sample_items=tf_sample_items,
                             remove_accidental_hits=True)
+
+
+class WARPLossGraph(AbstractLossGraph):
+    """
+    WARP, the weighted approximate-rank pairwise loss (Weston et al., "WSABIE"; the loss LightFM calls "warp"); not in the reference.
+    For every POSITIVE interaction p = (u, i) the user's sampled items are tried in table order; the first sample s whose margin is
+    violated, v = 1 - yhat_p + yhat[u, s] > 0, gives
+        loss_p = log(max((n_items - 1) div N_p, 1)) * v,        N_p = the number of trials up to and including s
+    and a positive without a violator among the samples has loss 0.  The rank weight is piecewise constant and is not differentiated,
+    so a step moves ONE sample per positive.  Magnitudes are ignored, negative interactions are ignored.  A sampled item that happens
+    to be one of the user's positives is kept as a trial: the sampler's contract, the same as for WMRB and BPR.
+    ``remove_accidental_hits=True`` skips those samples: a skipped hit is no trial.  Returns the [n_positive_interactions] vector.
+    csrc/loss_warp.hip; docs/sampled_losses.md, "WARP".
+    """
+    is_sample_based = True
+    is_sampled_with_replacement = False
+
+    remove_accidental_hits = False                               # (a pickle without the attribute)
+
+    def __init__(self, remove_accidental_hits=False):
+        self.remove_accidental_hits = _as_bool("remove_accidental_hits", remove_accidental_hits)
+        self.wants_sample_items = self.remove_accidental_hits
+
+    def connect_loss_graph(self, tf_prediction_serial, tf_interactions, tf_sample_predictions, tf_sample_items=None, **kwargs):
+        if not self.remove_accidental_hits:
+            return ops.warp_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions)
+        return ops.warp_loss(tf_prediction_serial, tf_sample_predictions, tf_interactions, sample_items=tf_sample_items,
+                             remove_accidental_hits=True)

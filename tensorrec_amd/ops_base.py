@@ -858,6 +858,36 @@ class _BPRAdjusted(torch.autograd.Function):
         return dp, ds, None, None
 
 
+class _WARP(torch.autograd.Function):
+    """trec_warp_fwd / _bwd; ``items``: the int32 sample ids when accidental hits are removed, else None"""
+
+    @staticmethod
+    def forward(ctx, pred_serial, sample_pred, inter: Interactions, items):
+        pred_serial, sample_pred = _f32c(pred_serial), _f32c(sample_pred)
+        n_users, n_items = inter.shape
+        S = sample_pred.shape[1]
+        dev = pred_serial.device
+        loss = torch.empty((inter.n_positive,), dtype=torch.float32, device=dev)
+        first = torch.empty((pred_serial.numel(),), dtype=torch.int32, device=dev)
+        weight = torch.empty((pred_serial.numel(),), dtype=torch.float32, device=dev)
+        hits = items is not None
+        N.call("trec_warp_fwd", N.ptr(inter.indptr), N.ptr(inter.x_item32) if hits else None, N.ptr(inter.pos_slot), N.ptr(pred_serial),
+               N.ptr(sample_pred), N.ptr(items), n_users, n_items, S, 1 if hits else 0, N.ptr(loss), N.ptr(first), N.ptr(weight))
+        ctx.inter, ctx.sample_shape = inter, tuple(sample_pred.shape)
+        ctx.save_for_backward(first, weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        first, weight = ctx.saved_tensors
+        inter = ctx.inter
+        dp = torch.empty_like(weight)
+        ds = torch.empty(ctx.sample_shape, dtype=torch.float32, device=weight.device)
+        N.call("trec_warp_bwd", N.ptr(inter.indptr), N.ptr(inter.pos_slot), N.ptr(first), N.ptr(weight), N.ptr(_f32c(gl)),
+               inter.shape[0], ctx.sample_shape[1], N.ptr(dp), N.ptr(ds))
+        return dp, ds, None, None
+
+
 import os as _os
 
 # sampled pairs from which the rank-free binned grouping replaces histogram atomics + ranked fill (TREC_BINNED_MIN_PAIRS: A/B runs)
@@ -1365,6 +1395,17 @@ def bpr_loss(pred_serial, sample_pred, interactions, sample_items=None, sample_l
     if not remove_accidental_hits:
         return _BPR.apply(pred_serial, sample_pred, interactions)
     return _BPRAdjusted.apply(pred_serial, sample_pred, interactions, _checked_sample_items(sample_items, sample_pred))
+
+
+def warp_loss(pred_serial, sample_pred, interactions, sample_items=None, remove_accidental_hits=False):
+    """[n_positive] vector of the WARP loss (csrc/loss_warp.hip): a user's samples are tried in table order, the first one with
+    v = (1 - y_p) + y_us > 0 gives loss_p = log(max((n_items - 1) div N_p, 1)) * v, N_p the number of trials up to it; no violator:
+    0.  The rank weight is not differentiated.  ``remove_accidental_hits`` as for bpr_loss: a hit is no trial.  n_items is
+    ``interactions.shape[1]``."""
+    if sample_pred.shape[0] != interactions.shape[0]:
+        raise ValueError("tf_sample_predictions must have one row per user")
+    items = _checked_sample_items(sample_items, sample_pred) if remove_accidental_hits else None
+    return _WARP.apply(pred_serial, sample_pred, interactions, items)
 
 
 class _RMSE(torch.autograd.Function):

@@ -39,7 +39,7 @@ from .errors import (
 from .framework import VariableStore, variable_scope, resolve_device
 from .loss_graphs import (AbstractLossGraph, RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph,
                           BalancedWMRBLossGraph, SeparationLossGraph, SeparationDenseLossGraph, SampledSoftmaxLossGraph,
-                          BPRLossGraph, SoftmaxDenseLossGraph)
+                          BPRLossGraph, SoftmaxDenseLossGraph, WARPLossGraph)
 from .prediction_graphs import AbstractPredictionGraph, DotProductPredictionGraph
 from .recommendation_graphs import (
     project_biases, bias_prediction_dense, bias_prediction_serial, rank_predictions,
@@ -1941,7 +1941,7 @@ class TensorRec(object):
 # (every built-in loss is made of this library's launches only: the separation losses lost their boolean-mask host syncs when
 # they became streaming reductions, csrc/loss_dense.hip)
 _GRAPH_CAPTURABLE_LOSSES = (RMSELossGraph, RMSEDenseLossGraph, WMRBLossGraph, BalancedWMRBLossGraph, SeparationLossGraph,
-                            SeparationDenseLossGraph, SampledSoftmaxLossGraph, BPRLossGraph)
+                            SeparationDenseLossGraph, SampledSoftmaxLossGraph, BPRLossGraph, WARPLossGraph)
 
 
 class _GraphedStep(object):
