@@ -693,6 +693,27 @@ int trec_softmax_fused_step(const float* U, const float* V, const float* user_bi
                             int32_t log_q_correction, int32_t remove_hits, float* loss, float* pred_serial, float* dU,
                             float* d_user_bias, float* coef_samples, float* coef_pairs, int32_t* sample_hist,
                             int32_t* sample_rank, void* stream);
+/* One training step's user side of the WARP loss in one pass (csrc/warp_fused.hip): the arguments, the outputs and the coverage of
+ * trec_softmax_fused_step -- gather, dU and the rank epilogue are the same code (csrc/user_fused_body.hpp) -- without the
+ * temperature and the logQ arguments and with the loss of trec_warp_fwd / _bwd at upstream gradient 1, through the one copy of its
+ * pieces in csrc/warp_common.hpp:  v_s = (1.0f - y_p) + y_s in this order, s violates iff v_s > 0 (strictly); f_p = the first
+ * kept violator in table order, N_p = the kept samples with index <= f_p, L_p = logf((float)max((n_items - 1) div N_p, 1)) (an
+ * exact 0 for a quotient <= 1);  loss_p = L_p v_f,  coef_pairs_p = -L_p,  coef_samples_us = sum_{p of u, f_p = s} L_p in
+ * interaction order;  an interaction with pos_slot < 0 or without a kept violator gets exact zeros.  remove_hits != 0: a sample
+ * whose item is the column of one of the user's interactions with pos_slot >= 0 is not kept (tested against the user's
+ * interaction ids on chip; the mask is per user).  first (nullable, int32 [n_interactions]): f_p, -1 where there is none.
+ * It replaces trec_pair_score_fwd on both pair lists, trec_warp_fwd / _bwd and the user side of the pair backward: every item row
+ * of a user is gathered once.  No float atomics: two calls give the same bits.  Errors before any launch: TREC_ERR_INVALID for
+ * null pointers, user_bias without d_user_bias or the reverse, sample_rank without sample_hist, n_items outside [1, 2^31), null
+ * interaction arrays with remove_hits; TREC_ERR_UNSUPPORTED for a shape trec_warp_fused_lds_bytes answers with -1 (then run the
+ * generic step).  n_users == 0: TREC_OK, no launch. */
+int trec_warp_fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d);
+int trec_warp_fused_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
+                         const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const int32_t* samples,
+                         int64_t n_users, int64_t n_items, int32_t n_sampled, int32_t d, int32_t max_interactions_per_user,
+                         int32_t remove_hits, float* loss, float* pred_serial, float* dU, float* d_user_bias,
+                         float* coef_samples, float* coef_pairs, int32_t* first, int32_t* sample_hist, int32_t* sample_rank,
+                         void* stream);
 /* The sampled softmax with ONE set of n_sampled negatives shared by every user of the step (csrc/softmax_shared.hip): the sample rows
  * are one gathered [n_sampled, d] matrix Vs with biases sample_bias (nullable) and logit constants sample_c (nullable: 0), and
  * w_us = ((U_u . Vs_s + user_bias_u) + sample_bias_s) inv_temperature + sample_c_s is formed tile by tile on fp32 MFMAs

@@ -17,6 +17,7 @@
 // The forward pass stores f_p (first) and L_p (weight) per interaction; the backward pass reads those and no prediction.
 // No expf / log1pf / division per cell: a compare and a ballot per 64 samples, one integer division and one logf per positive.
 #include "common.hpp"
+#include "warp_common.hpp"       // wp_weight, wp_upto, wp_hit: shared with csrc/warp_fused.hip
 
 #define WP_WAVE_SR 4               // samples per lane of the wave-per-user form: S <= 64 * WP_WAVE_SR
 #define WP_STAGE 256               // positives staged per pass of the workgroup backward kernel
@@ -36,15 +37,7 @@ __device__ __forceinline__ bool wp_is_hit(const int32_t* __restrict__ x_item, co
         const int64_t mid = (lo + hi) >> 1;
         if (x_item[mid] < item) lo = mid + 1; else hi = mid;
     }
-    return lo < e && x_item[lo] == item && pos_slot[lo] >= 0;
-}
-
-__device__ __forceinline__ uint64_t wp_upto(int k) { return (2ull << k) - 1ull; }        // bits 0..k (k = 63: all)
-
-__device__ __forceinline__ float wp_weight(int32_t n_items_m1, int32_t n_trials)
-{
-    const int32_t r = n_items_m1 / n_trials;
-    return r > 1 ? logf((float)r) : 0.f;
+    return lo < e && wp_hit(x_item[lo], pos_slot[lo], item);
 }
 
 // one user's samples into LDS (four loads per thread in flight, then the four LDS stores, as loss.hip fills)
@@ -63,7 +56,7 @@ __device__ __forceinline__ void wp_fill_samples(float* l_s, const float* __restr
 // Samples sit in <= 4 registers per lane (sample s = r * 64 + lane), padded with -inf: v = (1 - y_p) + -inf never violates.  The
 // positives are loaded 64 per pass and taken in turn; everything per positive is wave-uniform: a compare and a ballot per register,
 // the first set bit, a popcount of the kept ballots up to it.  Lane q keeps positive q's result, so the pass ends in coalesced stores.
-// HITS: a row of <= 64 interactions is held in registers -- lane i column i (INT32_MAX beyond the row) and whether it is a positive --
+// HITS: a row of <= 64 interactions is held in registers -- lane i column i (INT32_MAX beyond the row) and its pos_slot --
 // and searched with lane shuffles, a branchless six-step lower bound; longer rows take the binary search in memory.
 template <bool HITS>
 __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
@@ -82,10 +75,10 @@ __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
     uint64_t kept[WP_WAVE_SR];
     if (HITS) {
         const bool whole = e - b <= 64;                            // (wave-uniform)
-        int32_t col = 0x7fffffff, is_pos = 0;
+        int32_t col = 0x7fffffff, col_slot = -1;
         if (whole && b + lane < e) {
             col = h.x_item[b + lane];
-            is_pos = pos_slot[b + lane] >= 0;
+            col_slot = pos_slot[b + lane];
         }
 #pragma unroll
         for (int r = 0; r < WP_WAVE_SR; ++r) {
@@ -99,8 +92,8 @@ __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
 #pragma unroll
                 for (int step = 32; step > 0; step >>= 1)
                     if (__shfl(col, at_row + step - 1, 64) < item) at_row += step;
-                const int32_t at_col = __shfl(col, at_row, 64), at_pos = __shfl(is_pos, at_row, 64);      // (both by every lane)
-                hit = at_col == item && at_pos != 0;
+                const int32_t at_col = __shfl(col, at_row, 64), at_slot = __shfl(col_slot, at_row, 64);   // (both by every lane)
+                hit = wp_hit(at_col, at_slot, item);
             } else {
                 hit = live && wp_is_hit(h.x_item, pos_slot, b, e, item);
             }

@@ -8,7 +8,7 @@ _CoopStep.plan and TensorRec._graph_eligible gather the inputs; the shapes a ker
 from collections import namedtuple
 
 from . import ops
-from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph, SoftmaxDenseLossGraph
+from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph, SoftmaxDenseLossGraph, WARPLossGraph
 
 Switches = namedtuple("Switches", "wmrb_fused wmrb_tiled softmax_fused softmax_shared fit_step_coop")
 # only the exact built-in classes have a kind: a subclass may override anything the kernels restate
@@ -75,6 +75,27 @@ def dense_kernel(loss, engine, engine_mode, multi, same_width, n_items, d, switc
         return None
     on = ops.step_switch("softmax_full") if switch is None else switch
     return "softmax_full" if on else None
+
+
+def warp_loss_kind(loss_graph):
+    """"warp" for an instance of exactly WARPLossGraph, None for everything else (a subclass may override anything the kernel
+    restates).  Apart from ``kernel``'s table, as dense_loss_kind is: the one-pass WARP step is opt-in and LOSS_KINDS names the
+    losses whose one-pass step is the default."""
+    return "warp" if type(loss_graph) is WARPLossGraph else None
+
+
+def warp_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz, d, switch=None):
+    """The one-pass kernel of a training step under the WARP loss -- "warp_fused" (csrc/warp_fused.hip, ops.warp_fused_step) -- or
+    None: the generic step.  ``loss``: warp_loss_kind's answer; the guards are those of the sampled softmax in ``kernel`` -- a
+    built-in prediction graph in MODE_DOT (cosine counts as dot: the step is fed the normalised operands), one taste, both
+    representations 2-D and equally wide (``d`` that width), ``n_sampled`` given --, then the shape must be covered
+    (ops.step_covers) and the switch on; ``switch``: tuning "warp_fused", None reads the library's (ops.WARP_FUSED_DEFAULT: off)."""
+    if loss != "warp" or not engine or engine_mode != ops.MODE_DOT or multi or not same_width or n_sampled is None:
+        return None
+    if not ops.step_covers("warp_fused", n_sampled, max_row_nnz, d):
+        return None
+    on = ops.step_switch("warp_fused") if switch is None else switch
+    return "warp_fused" if on else None
 
 
 def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,

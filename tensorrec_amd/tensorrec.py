@@ -379,7 +379,8 @@ class TensorRec(object):
         self._graph_pool_owner = []
         self.last_route = None        # what predict_top_k did last (route report)
         self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused",
-                                      # "softmax_shared", "softmax_full" (step_plan.dense_kernel);
+                                      # "softmax_shared", "softmax_full" (step_plan.dense_kernel), "warp_fused" (step_plan.warp_kernel:
+                                      # only with tuning warp_fused = 1);
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -806,6 +807,9 @@ class TensorRec(object):
                 a_ins = [ops.l2_normalize_rows(a) for a in attn_reprs] if attn_reprs is not None else None
                 i_in = ops.l2_normalize_rows(item_repr)
             u_in = u_ins[0]
+            if kernel is None:          # the WARP loss: its one-pass step is opt-in (tuning warp_fused), apart from kernel()'s table
+                kernel = step_plan.warp_kernel(step_plan.warp_loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi,
+                                               same_width, n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]))
             if kernel is not None:
                 return self._one_pass_step(kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                            n_sampled_items, want_stats, samples, apply)
@@ -911,6 +915,8 @@ class TensorRec(object):
             out = ops.wmrb_fused_step(*operands, samples, balanced=loss_graph.balanced)
         elif kernel == "wmrb_tiled":
             out = ops.wmrb_tiled_step(*operands, samples, balanced=loss_graph.balanced, mode=self.prediction_graph_factory.engine_mode)
+        elif kernel == "warp_fused":
+            out = ops.warp_fused_step(*operands, samples, remove_accidental_hits=loss_graph.remove_accidental_hits)
         else:
             log_q = getattr(self.sampler, 'log_q', None)
             options = dict(sample_log_q=log_q(self._store.device) if callable(log_q) else None,
