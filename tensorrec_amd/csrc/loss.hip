@@ -11,7 +11,7 @@
 // The second sum is done with threads owning s and looping over p (no atomics, fixed order -> deterministic).
 //
 // RMSE (loss_graphs.py:58-59): sqrt(mean((y - yhat)^2)); backward d yhat_p = go * -(y_p - yhat_p) / (P * loss).
-#include "common.hpp"
+#include "sampled_common.hpp"   // FILL_SAMPLES and the launch forms
 
 #define WMRB_MAX_POS_LDS 1024      // positives of one user staged per pass
 
@@ -26,14 +26,7 @@ __global__ __launch_bounds__(256) void wmrb_fwd_kernel(
     const int64_t u = blockIdx.x;
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    // (four loads per thread in flight, then the four LDS stores: a load -> store loop waits for every load on its own)
-    for (int s0 = threadIdx.x; s0 < S; s0 += 1024) {
-        float t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; t[k] = samp[u * S + (s < S ? s : S - 1)]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; if (s < S) lds[s] = t[k]; }
-    }
+    FILL_SAMPLES(lds, samp, u, S);
     __syncthreads();
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     for (int64_t p = b + wave; p < e; p += 4) {
@@ -64,13 +57,7 @@ __global__ __launch_bounds__(256) void wmrb_bwd_kernel(
     float* l_c = l_yp + WMRB_MAX_POS_LDS;
     const int64_t u = blockIdx.x;
     const int64_t b = indptr[u], e = indptr[u + 1];
-    for (int s0 = threadIdx.x; s0 < S; s0 += 1024) {         // (batched like the forward kernel's fill)
-        float t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; t[k] = samp[u * S + (s < S ? s : S - 1)]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; if (s < S) l_s[s] = t[k]; }
-    }
+    FILL_SAMPLES(l_s, samp, u, S);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     // per-thread accumulators for the samples this thread owns (s = tid, tid+256, ...): kept in LDS-free registers
     // by walking sample blocks of 256 at a time in the outer loop below.
@@ -119,8 +106,6 @@ __global__ __launch_bounds__(256) void wmrb_bwd_kernel(
 // and the launch is bound by workgroup dispatch (1M workgroups).  Here a wave owns a user: the samples sit in <= 4
 // registers per lane (sample s = r*64 + lane, the same lane/order split as the workgroup kernels, so results are
 // bit-identical), the user's positives are loaded by the lanes in parallel (64 per pass) and broadcast with readlane.
-#define WMRB_WAVE_SR 4
-
 __global__ __launch_bounds__(256) void wmrb_fwd_wave_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pos_weight,
     const float* __restrict__ pred, const float* __restrict__ samp, int64_t n_users, int32_t S, float ratio,
@@ -131,9 +116,9 @@ __global__ __launch_bounds__(256) void wmrb_fwd_wave_kernel(
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    float ys[WMRB_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < WMRB_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
     for (int64_t p0 = b; p0 < e; p0 += 64) {
         const int np = (int)((e - p0 < 64) ? (e - p0) : 64);
         int32_t slot = -1;
@@ -149,7 +134,7 @@ __global__ __launch_bounds__(256) void wmrb_fwd_wave_kernel(
             const float base = 1.0f - __shfl(yp, q, 64);
             float acc = 0.f;
 #pragma unroll
-            for (int r = 0; r < WMRB_WAVE_SR; ++r) acc += fmaxf(base + ys[r], 0.f);     // -inf padding adds 0
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r) acc += fmaxf(base + ys[r], 0.f);     // -inf padding adds 0
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
             if (lane == q) my_smr = ratio * acc;
         }
@@ -171,9 +156,9 @@ __global__ __launch_bounds__(256) void wmrb_bwd_wave_kernel(
     if (u >= n_users) return;
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
-    float ys[WMRB_WAVE_SR], acc[WMRB_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR], acc[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < WMRB_WAVE_SR; ++r) {
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
         ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
         acc[r] = 0.f;
     }
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(256) void wmrb_bwd_wave_kernel(
             const float base = 1.0f - __shfl(yp, q, 64);
             int cnt = 0;
 #pragma unroll
-            for (int r = 0; r < WMRB_WAVE_SR; ++r) {
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
                 const bool active = base + ys[r] >= 0.f;           // -inf padding is never active
                 cnt += __popcll(__builtin_amdgcn_ballot_w64(active));
                 acc[r] += active ? cq : 0.f;
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(256) void wmrb_bwd_wave_kernel(
         if (lane < np) d_pred[p0 + lane] = my_dp;
     }
 #pragma unroll
-    for (int r = 0; r < WMRB_WAVE_SR; ++r)
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r)
         if (r * 64 + lane < S) d_samp[u * S + r * 64 + lane] = acc[r];
 }
 
@@ -264,8 +249,8 @@ extern "C" int trec_wmrb_fwd(const int64_t* indptr, const int32_t* pos_slot, con
     TREC_REQUIRE(n_sampled >= 1 && n_sampled <= 16384, "trec_wmrb_fwd: n_sampled must be in [1, 16384]");
     if (n_users == 0) return TREC_OK;
     const float ratio = (float)n_items / (float)n_sampled;
-    if (n_sampled <= 64 * WMRB_WAVE_SR && trec_get_tuning("wmrb_wave", 1)) {
-        hipLaunchKernelGGL(wmrb_fwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0,
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(wmrb_fwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0,
                            (hipStream_t)stream, indptr, pos_slot, pos_weight, pred_serial, sample_pred, n_users, n_sampled,
                            ratio, loss, smr);
         return trec_check_launch("trec_wmrb_fwd");
@@ -286,8 +271,8 @@ extern "C" int trec_wmrb_bwd(const int64_t* indptr, const int32_t* pos_slot, con
     TREC_REQUIRE(n_sampled >= 1 && n_sampled <= 16384, "trec_wmrb_bwd: n_sampled must be in [1, 16384]");
     if (n_users == 0) return TREC_OK;
     const float ratio = (float)n_items / (float)n_sampled;
-    if (n_sampled <= 64 * WMRB_WAVE_SR && trec_get_tuning("wmrb_wave", 1)) {
-        hipLaunchKernelGGL(wmrb_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0,
+    if (use_wave_form(n_sampled)) {
+        hipLaunchKernelGGL(wmrb_bwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0,
                            (hipStream_t)stream, indptr, pos_slot, pos_weight, pred_serial, sample_pred, smr, grad_loss,
                            n_users, n_sampled, ratio, d_pred_serial, d_sample_pred);
         return trec_check_launch("trec_wmrb_bwd");

@@ -13,7 +13,7 @@
 // double (per thread, per wave by shuffles, one atomicAdd per workgroup), so the result does not depend on the reduction order
 // beyond 1e-12; the model tests hold it to 1e-5 of the reference's own arithmetic (fixtures made by running the reference's source),
 // tests/test_gpu_dense_losses.py holds every entry point to 1e-11 of a float64 restatement (st, coef) and to float32 rounding (outputs).
-#include "common.hpp"
+#include "sampled_common.hpp"   // temperature_ok
 #include <math.h>
 
 namespace {
@@ -555,7 +555,6 @@ extern "C" int trec_dense_loss_factored_bwd(int32_t kind, const float* pred_seri
 // The full softmax over the catalogue on a dense prediction (SoftmaxDenseLossGraph, generic form; formulas above the kernels).
 // pred [n_users, n_items] with row stride ld >= n_items; the interactions as CSR over users (indptr, x_item sorted within a row,
 // pos_slot < 0: not a positive); loss [P+], row_max / row_sum [n_users] kept for the backward pass.
-static bool sd_temperature_ok(float inv_temperature) { return inv_temperature > 0.f && inv_temperature <= 3.402823466e+38f; }
 
 extern "C" int trec_softmax_dense_fwd(const float* pred, int64_t ld, const int64_t* indptr, const int32_t* x_item,
                                       const int32_t* pos_slot, int64_t n_users, int64_t n_items, float inv_temperature, float* loss,
@@ -564,7 +563,7 @@ extern "C" int trec_softmax_dense_fwd(const float* pred, int64_t ld, const int64
     TREC_REQUIRE(pred && indptr && x_item && pos_slot && loss && row_max && row_sum, "trec_softmax_dense_fwd: null pointer");
     TREC_REQUIRE(n_items >= 1 && n_items < ((int64_t)1 << 31) && ld >= n_items, "trec_softmax_dense_fwd: need 1 <= n_items < 2^31 and ld >= n_items");
     TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_dense_fwd: n_users must lie in [0, 2^31)");
-    TREC_REQUIRE(sd_temperature_ok(inv_temperature), "trec_softmax_dense_fwd: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_dense_fwd: inv_temperature must be finite and > 0");
     if (n_users == 0) return TREC_OK;
     if (n_items <= SD_WAVE_MAX_ITEMS)
         hipLaunchKernelGGL(softmax_dense_fwd_kernel<64>, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -583,7 +582,7 @@ extern "C" int trec_softmax_dense_bwd(const float* pred, int64_t ld, const int64
     TREC_REQUIRE(pred && indptr && x_item && pos_slot && row_max && row_sum && grad_loss && d_pred, "trec_softmax_dense_bwd: null pointer");
     TREC_REQUIRE(n_items >= 1 && n_items < ((int64_t)1 << 31) && ld >= n_items, "trec_softmax_dense_bwd: need 1 <= n_items < 2^31 and ld >= n_items");
     TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_dense_bwd: n_users must lie in [0, 2^31)");
-    TREC_REQUIRE(sd_temperature_ok(inv_temperature), "trec_softmax_dense_bwd: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_dense_bwd: inv_temperature must be finite and > 0");
     if (n_users == 0) return TREC_OK;
     if (n_items <= SD_WAVE_MAX_ITEMS)
         hipLaunchKernelGGL(softmax_dense_bwd_kernel<64>, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,

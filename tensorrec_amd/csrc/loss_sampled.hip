@@ -16,64 +16,9 @@
 //     backward          d y_p = -(go_p / S) sum_s sigma(y_s - y_p),   d y_us = (1/S) sum_p go_p sigma(y_us - y_p)
 //                       sigma(x) = x >= 0 ? 1 / (1 + e) : e / (1 + e),  e = exp(-|x|)
 //     O(S n_u) like WMRB, and WMRB's loop structure: threads own samples and loop over the staged positives in order.
-#include "common.hpp"
+#include "sampled_common.hpp"   // the hit rule, ssm_terms, logq_correction, fill_samples, the reductions, the launch forms
 
 #define SL_MAX_POS_LDS 1024        // positives of one user staged per pass (workgroup BPR backward)
-#define SL_WAVE_SR 4               // samples per lane of the wave-per-user forms: S <= 64 * SL_WAVE_SR
-
-// ---- shared pieces ------------------------------------------------------------------------------------------
-// fixed-tree workgroup reductions over 256 threads (every thread gets the result)
-__device__ __forceinline__ float wg_sum(float v, float* red)
-{
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-__device__ __forceinline__ float wg_max(float v, float* red)
-{
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    return red[0];
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// one user's samples into LDS (four loads per thread in flight, then the four LDS stores, as loss.hip fills)
-__device__ __forceinline__ void fill_samples(float* l_s, const float* __restrict__ samp, int64_t u, int32_t S)
-{
-    for (int s0 = threadIdx.x; s0 < S; s0 += 1024) {
-        float t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; t[k] = samp[u * S + (s < S ? s : S - 1)]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; if (s < S) l_s[s] = t[k]; }
-    }
-}
-
-// the per-positive terms of the sampled softmax from the user's (M, Z): bz = b Z, D = a + b Z; forward and backward share the code
-__device__ __forceinline__ void ssm_terms(float yp, float M, float Z, float t, float& m, float& b, float& bz, float& D)
-{
-    m = fmaxf(M, yp);
-    const float a = expf((yp - m) * t);
-    b = expf((M - m) * t);
-    bz = b * Z;
-    D = a + bz;
-}
 
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
@@ -103,17 +48,6 @@ struct SlAdj {
     int32_t flags;
 };
 
-__device__ __forceinline__ bool sl_is_hit(const int32_t* __restrict__ x_item, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e,
-                                          int32_t item)
-{
-    int64_t lo = b, hi = e;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (x_item[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < e && x_item[lo] == item && pos_slot[lo] >= 0;
-}
-
 // prediction y of the sample at flat position `at` of user row [b, e): -inf when it is a hit, else y with its correction in c
 __device__ __forceinline__ float sl_adjust(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e, int64_t at,
                                            float y, float& c)
@@ -121,33 +55,24 @@ __device__ __forceinline__ float sl_adjust(const SlAdj& adj, const int32_t* __re
     c = 0.f;
     if (adj.flags == 0) return y;
     const int32_t item = adj.samples[at];
-    if ((adj.flags & SL_ADJ_HITS) && sl_is_hit(adj.x_item, pos_slot, b, e, item)) return -INFINITY;
+    if ((adj.flags & SL_ADJ_HITS) && row_is_hit(adj.x_item, pos_slot, b, e, item)) return -INFINITY;
     if ((adj.flags & SL_ADJ_LOGQ) && (uint32_t)item < (uint32_t)adj.n_items)
-        c = -(adj.log_s + (adj.log_q ? adj.log_q[item] : adj.log_q_uniform));
+        c = logq_correction(adj.log_s, adj.log_q ? adj.log_q[item] : adj.log_q_uniform);
     return y;
 }
 
-// The wave-per-user forms keep a row of at most 64 interactions in registers -- lane i holds column i (INT32_MAX beyond the row) and
-// whether it is a positive -- and search it with lane shuffles instead of memory loads: a branchless lower bound, six steps.  Every
-// lane of the wave calls sl_adjust_wave (a lane without a sample passes live = false and gets its -inf padding back); longer rows
-// take the binary search in memory.  The conditions on adj.flags and row.whole are wave-uniform.
-struct SlRow { int32_t col; int32_t pos; bool whole; };
-
-__device__ __forceinline__ SlRow sl_row_wave(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e, int lane)
+// The wave-per-user forms search a row of at most 64 interactions in registers (HitRow).  Every lane of the wave calls sl_adjust_wave
+// (a lane without a sample passes live = false and gets its -inf padding back); longer rows take the binary search in memory.  The
+// conditions on adj.flags and row.whole are wave-uniform.
+__device__ __forceinline__ HitRow sl_row_wave(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e, int lane)
 {
-    SlRow row;
-    row.whole = e - b <= 64;
-    row.col = 0x7fffffff;
-    row.pos = 0;
-    if ((adj.flags & SL_ADJ_HITS) && row.whole && b + lane < e) {
-        row.col = adj.x_item[b + lane];
-        row.pos = pos_slot[b + lane] >= 0;
-    }
+    HitRow row;
+    HIT_ROW_LOAD(row.whole, row.col, row.slot, adj.flags & SL_ADJ_HITS, adj.x_item, pos_slot, b, e, lane);
     return row;
 }
 
 __device__ __forceinline__ float sl_adjust_wave(const SlAdj& adj, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e,
-                                                const SlRow& row, bool live, int64_t at, float y, float& c)
+                                                const HitRow& row, bool live, int64_t at, float y, float& c)
 {
     c = 0.f;
     if (adj.flags == 0) return y;
@@ -155,19 +80,14 @@ __device__ __forceinline__ float sl_adjust_wave(const SlAdj& adj, const int32_t*
     if (adj.flags & SL_ADJ_HITS) {
         bool hit;
         if (row.whole) {
-            int at_row = 0;                                         // columns [0, at_row) are below the item
-#pragma unroll
-            for (int step = 32; step > 0; step >>= 1)
-                if (__shfl(row.col, at_row + step - 1, 64) < item) at_row += step;
-            const int32_t col = __shfl(row.col, at_row, 64), is_pos = __shfl(row.pos, at_row, 64);
-            hit = col == item && is_pos != 0;
+            HIT_ROW_TEST(hit, row.col, row.slot, item);
         } else {
-            hit = live && sl_is_hit(adj.x_item, pos_slot, b, e, item);
+            hit = live && row_is_hit(adj.x_item, pos_slot, b, e, item);
         }
         if (hit) return -INFINITY;
     }
     if (live && (adj.flags & SL_ADJ_LOGQ) && (uint32_t)item < (uint32_t)adj.n_items)
-        c = -(adj.log_s + (adj.log_q ? adj.log_q[item] : adj.log_q_uniform));
+        c = logq_correction(adj.log_s, adj.log_q ? adj.log_q[item] : adj.log_q_uniform);
     return y;
 }
 
@@ -184,14 +104,14 @@ __global__ __launch_bounds__(256) void ssm_fwd_wave_kernel(
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    float ys[SL_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
     float M = fmaxf(fmaxf(ys[0], ys[1]), fmaxf(ys[2], ys[3]));
     for (int off = 32; off > 0; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, 64));
     float z = 0.f;
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) z += expf((ys[r] - M) * t);
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) z += expf((ys[r] - M) * t);
     const float Z = wave_sum(z);
     if (lane == 0) { Mu[u] = M; Zu[u] = Z; }
     for (int64_t p = b + lane; p < e; p += 64) {
@@ -241,7 +161,7 @@ __global__ __launch_bounds__(256) void ssm_bwd_wave_kernel(
         }
     }
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) {
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
         const int s = r * 64 + lane;
         if (s < S) d_samp[u * S + s] = any ? (t * expf((samp[u * S + s] - M) * t)) * K : 0.f;
     }
@@ -263,10 +183,10 @@ __global__ __launch_bounds__(256) void ssm_fwd_kernel(
     __syncthreads();
     float mx = -INFINITY;
     for (int s = threadIdx.x; s < S; s += 256) mx = fmaxf(mx, lds[s]);
-    const float M = wg_max(mx, red);
+    const float M = wg_max_halving(mx, red);
     float z = 0.f;
     for (int s = threadIdx.x; s < S; s += 256) z += expf((lds[s] - M) * t);
-    const float Z = wg_sum(z, red);
+    const float Z = wg_sum_halving(z, red);
     if (threadIdx.x == 0) { Mu[u] = M; Zu[u] = Z; }
     for (int64_t p = b + threadIdx.x; p < e; p += 256) {
         const int32_t slot = pos_slot[p];
@@ -301,8 +221,8 @@ __global__ __launch_bounds__(256) void ssm_bwd_kernel(
         }
         d_pred[p] = dp;
     }
-    const float K = wg_sum(k, red);
-    const bool any = wg_max(n_pos, red) > 0.f;
+    const float K = wg_sum_halving(k, red);
+    const bool any = wg_max_halving(n_pos, red) > 0.f;
     for (int s = threadIdx.x; s < S; s += 256)
         d_samp[u * S + s] = any ? (t * expf((samp[u * S + s] - M) * t)) * K : 0.f;
 }
@@ -325,10 +245,10 @@ __global__ __launch_bounds__(256) void ssm_adj_fwd_wave_kernel(
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
-    float ys[SL_WAVE_SR], cs[SL_WAVE_SR];
+    const HitRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+    float ys[SAMPLED_WAVE_SR], cs[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) {
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
         const bool live = r * 64 + lane < S;
         ys[r] = sl_adjust_wave(adj, pos_slot, b, e, row, live, u * S + r * 64 + lane, live ? samp[u * S + r * 64 + lane] : -INFINITY, cs[r]);
     }
@@ -337,14 +257,14 @@ __global__ __launch_bounds__(256) void ssm_adj_fwd_wave_kernel(
     const bool none = R == -INFINITY;                              // wave-uniform: every sample is a hit
     float M = 0.f, Z = 0.f;
     if (!none) {
-        float w[SL_WAVE_SR];
+        float w[SAMPLED_WAVE_SR];
 #pragma unroll
-        for (int r = 0; r < SL_WAVE_SR; ++r) w[r] = (ys[r] - R) * t + cs[r];      // -inf for a hit or padding
+        for (int r = 0; r < SAMPLED_WAVE_SR; ++r) w[r] = (ys[r] - R) * t + cs[r];      // -inf for a hit or padding
         M = fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3]));
         for (int off = 32; off > 0; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, 64));
         float z = 0.f;
 #pragma unroll
-        for (int r = 0; r < SL_WAVE_SR; ++r) z += expf(w[r] - M);
+        for (int r = 0; r < SAMPLED_WAVE_SR; ++r) z += expf(w[r] - M);
         Z = wave_sum(z);
     }
     if (lane == 0) { Ru[u] = R; Mu[u] = M; Zu[u] = Z; }
@@ -400,9 +320,9 @@ __global__ __launch_bounds__(256) void ssm_adj_bwd_wave_kernel(
             for (int q = 0; q < np; ++q) K += __shfl(term, q, 64); // interaction order; a non-positive adds an exact 0
         }
     }
-    const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+    const HitRow row = sl_row_wave(adj, pos_slot, b, e, lane);
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) {
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
         const int s = r * 64 + lane;
         if (r * 64 >= S) continue;                                 // (wave-uniform)
         float d = 0.f;
@@ -436,7 +356,7 @@ __global__ __launch_bounds__(256) void ssm_adj_fwd_kernel(
         l_c[s] = c;
         mx = fmaxf(mx, y);
     }
-    const float R = wg_max(mx, red);
+    const float R = wg_max_halving(mx, red);
     const bool none = R == -INFINITY;
     float M = 0.f, Z = 0.f;
     if (!none) {
@@ -446,10 +366,10 @@ __global__ __launch_bounds__(256) void ssm_adj_fwd_kernel(
             l_w[s] = w;
             mx = fmaxf(mx, w);
         }
-        M = wg_max(mx, red);
+        M = wg_max_halving(mx, red);
         float z = 0.f;
         for (int s = threadIdx.x; s < S; s += 256) z += expf(l_w[s] - M);
-        Z = wg_sum(z, red);
+        Z = wg_sum_halving(z, red);
     }
     if (threadIdx.x == 0) { Ru[u] = R; Mu[u] = M; Zu[u] = Z; }
     for (int64_t p = b + threadIdx.x; p < e; p += 256) {
@@ -490,8 +410,8 @@ __global__ __launch_bounds__(256) void ssm_adj_bwd_kernel(
         }
         d_pred[p] = dp;
     }
-    const float K = wg_sum(k, red);
-    const bool any = wg_max(n_pos, red) > 0.f;
+    const float K = wg_sum_halving(k, red);
+    const bool any = wg_max_halving(n_pos, red) > 0.f;
     for (int s = threadIdx.x; s < S; s += 256) {
         float d = 0.f;
         if (any) {
@@ -513,20 +433,6 @@ __global__ __launch_bounds__(256) void ssm_adj_bwd_kernel(
 #undef SL_ADJ
 
 // ---- entry points ------------------------------------------------------------------------------------------------
-// dynamic LDS above 64 KB (S close to 16384) has to be asked for
-template <typename K>
-static inline void allow_lds(K kernel, size_t lds)
-{
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-static inline bool use_wave_form(int32_t n_sampled)
-{
-    return n_sampled <= 64 * SL_WAVE_SR && trec_get_tuning("wmrb_wave", 1);
-}
-
-static inline bool temperature_ok(float inv_temperature) { return inv_temperature > 0.f && inv_temperature <= 3.402823466e+38f; }
-
 extern "C" int trec_sampled_softmax_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial,
                                         const float* sample_pred, int64_t n_users, int32_t n_sampled, float inv_temperature,
                                         float* loss, float* row_max, float* row_sum, void* stream)
@@ -537,7 +443,7 @@ extern "C" int trec_sampled_softmax_fwd(const int64_t* indptr, const int32_t* po
     TREC_REQUIRE(temperature_ok(inv_temperature), "trec_sampled_softmax_fwd: inv_temperature must be finite and > 0");
     if (n_users == 0) return TREC_OK;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(ssm_fwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(ssm_fwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_temperature, loss, row_max, row_sum);
         return trec_check_launch("trec_sampled_softmax_fwd");
     }
@@ -559,7 +465,7 @@ extern "C" int trec_sampled_softmax_bwd(const int64_t* indptr, const int32_t* po
     TREC_REQUIRE(temperature_ok(inv_temperature), "trec_sampled_softmax_bwd: inv_temperature must be finite and > 0");
     if (n_users == 0) return TREC_OK;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(ssm_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(ssm_bwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, row_max, row_sum, grad_loss, n_users, n_sampled,
                            inv_temperature, d_pred_serial, d_sample_pred);
         return trec_check_launch("trec_sampled_softmax_bwd");
@@ -577,7 +483,7 @@ extern "C" int trec_bpr_fwd(const int64_t* indptr, const int32_t* pos_slot, cons
     if (n_users == 0) return TREC_OK;
     const float inv_s = 1.0f / (float)n_sampled;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(bpr_fwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(bpr_fwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_s, loss);
         return trec_check_launch("trec_bpr_fwd");
     }
@@ -598,7 +504,7 @@ extern "C" int trec_bpr_bwd(const int64_t* indptr, const int32_t* pos_slot, cons
     if (n_users == 0) return TREC_OK;
     const float inv_s = 1.0f / (float)n_sampled;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(bpr_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(bpr_bwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, grad_loss, n_users, n_sampled, inv_s, d_pred_serial,
                            d_sample_pred);
         return trec_check_launch("trec_bpr_bwd");
@@ -644,7 +550,7 @@ extern "C" int trec_sampled_softmax_adj_fwd(const int64_t* indptr, const int32_t
     if (n_users == 0) return TREC_OK;
     const SlAdj adj = make_adj(x_item, samples, log_q, log_q_uniform, n_items, n_sampled, log_q_correction, remove_hits);
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(ssm_adj_fwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(ssm_adj_fwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_temperature, loss, row_ref, row_max,
                            row_sum, adj);
         return trec_check_launch("trec_sampled_softmax_adj_fwd");
@@ -671,7 +577,7 @@ extern "C" int trec_sampled_softmax_adj_bwd(const int64_t* indptr, const int32_t
     if (n_users == 0) return TREC_OK;
     const SlAdj adj = make_adj(x_item, samples, log_q, log_q_uniform, n_items, n_sampled, log_q_correction, remove_hits);
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(ssm_adj_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(ssm_adj_bwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, row_ref, row_max, row_sum, grad_loss, n_users, n_sampled,
                            inv_temperature, d_pred_serial, d_sample_pred, adj);
         return trec_check_launch("trec_sampled_softmax_adj_bwd");
@@ -694,7 +600,7 @@ extern "C" int trec_bpr_adj_fwd(const int64_t* indptr, const int32_t* x_item, co
     const SlAdj adj = make_adj(x_item, samples, nullptr, 0.f, n_items, n_sampled, 0, remove_hits);
     const float inv_s = 1.0f / (float)n_sampled;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(bpr_fwd_wave_adj_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(bpr_fwd_wave_adj_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, n_users, n_sampled, inv_s, loss, adj);
         return trec_check_launch("trec_bpr_adj_fwd");
     }
@@ -718,7 +624,7 @@ extern "C" int trec_bpr_adj_bwd(const int64_t* indptr, const int32_t* x_item, co
     const SlAdj adj = make_adj(x_item, samples, nullptr, 0.f, n_items, n_sampled, 0, remove_hits);
     const float inv_s = 1.0f / (float)n_sampled;
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(bpr_bwd_wave_adj_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(bpr_bwd_wave_adj_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, pred_serial, sample_pred, grad_loss, n_users, n_sampled, inv_s, d_pred_serial,
                            d_sample_pred, adj);
         return trec_check_launch("trec_bpr_adj_bwd");

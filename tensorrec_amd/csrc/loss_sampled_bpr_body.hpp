@@ -22,14 +22,14 @@ __global__ __launch_bounds__(256) void SL_KERNEL(bpr_fwd_wave)(
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    float ys[SL_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
 #if SL_ADJ
     {                                                              // a hit becomes padding
-        const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+        const HitRow row = sl_row_wave(adj, pos_slot, b, e, lane);
 #pragma unroll
-        for (int r = 0; r < SL_WAVE_SR; ++r) {
+        for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
             float c;
             ys[r] = sl_adjust_wave(adj, pos_slot, b, e, row, r * 64 + lane < S, u * S + r * 64 + lane, ys[r], c);
         }
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void SL_KERNEL(bpr_fwd_wave)(
             const float ypq = __shfl(yp, q, 64);
             float acc = 0.f;
 #pragma unroll
-            for (int r = 0; r < SL_WAVE_SR; ++r)
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r)
                 if (r * 64 < S) acc += softplus_f(ys[r] - ypq);    // (wave-uniform: a register of padding only costs nothing)
             acc = wave_sum(acc);
             if (lane == q) mine = acc * inv_s;
@@ -67,17 +67,17 @@ __global__ __launch_bounds__(256) void SL_KERNEL(bpr_bwd_wave)(
     if (u >= n_users) return;
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
-    float ys[SL_WAVE_SR], acc[SL_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR], acc[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r) {
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
         ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
         acc[r] = 0.f;
     }
 #if SL_ADJ
     {                                                              // a hit becomes padding
-        const SlRow row = sl_row_wave(adj, pos_slot, b, e, lane);
+        const HitRow row = sl_row_wave(adj, pos_slot, b, e, lane);
 #pragma unroll
-        for (int r = 0; r < SL_WAVE_SR; ++r) {
+        for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
             float c;
             ys[r] = sl_adjust_wave(adj, pos_slot, b, e, row, r * 64 + lane < S, u * S + r * 64 + lane, ys[r], c);
         }
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void SL_KERNEL(bpr_bwd_wave)(
             const float ypq = __shfl(yp, q, 64);
             float sg = 0.f;
 #pragma unroll
-            for (int r = 0; r < SL_WAVE_SR; ++r) {
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
                 if (r * 64 >= S) continue;                         // (wave-uniform: a register of padding only costs nothing)
                 const float sig = sigmoid_f(ys[r] - ypq);
                 sg += sig;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void SL_KERNEL(bpr_bwd_wave)(
         if (lane < np) d_pred[p0 + lane] = my_dp;
     }
 #pragma unroll
-    for (int r = 0; r < SL_WAVE_SR; ++r)
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r)
         if (r * 64 + lane < S) d_samp[u * S + r * 64 + lane] = acc[r];
 }
 

@@ -16,10 +16,8 @@
 //            the sum in interaction order
 // The forward pass stores f_p (first) and L_p (weight) per interaction; the backward pass reads those and no prediction.
 // No expf / log1pf / division per cell: a compare and a ballot per 64 samples, one integer division and one logf per positive.
-#include "common.hpp"
-#include "warp_common.hpp"       // wp_weight, wp_upto, wp_hit: shared with csrc/warp_fused.hip
+#include "warp_common.hpp"       // wp_weight, wp_upto: shared with csrc/warp_fused.hip; the hit rule and the launch forms of sampled_common.hpp
 
-#define WP_WAVE_SR 4               // samples per lane of the wave-per-user form: S <= 64 * WP_WAVE_SR
 #define WP_STAGE 256               // positives staged per pass of the workgroup backward kernel
 
 // ---- shared pieces ------------------------------------------------------------------------------------------
@@ -28,36 +26,11 @@ struct WpHits {
     const int32_t* samples;     // [n_users, S] sampled item ids
 };
 
-// the hit test of loss_sampled.hip: one binary search over the user's columns, then pos_slot of the match (a value <= 0 is no hit)
-__device__ __forceinline__ bool wp_is_hit(const int32_t* __restrict__ x_item, const int32_t* __restrict__ pos_slot, int64_t b, int64_t e,
-                                          int32_t item)
-{
-    int64_t lo = b, hi = e;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (x_item[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < e && wp_hit(x_item[lo], pos_slot[lo], item);
-}
-
-// one user's samples into LDS (four loads per thread in flight, then the four LDS stores, as loss.hip fills)
-__device__ __forceinline__ void wp_fill_samples(float* l_s, const float* __restrict__ samp, int64_t u, int32_t S)
-{
-    for (int s0 = threadIdx.x; s0 < S; s0 += 1024) {
-        float t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; t[k] = samp[u * S + (s < S ? s : S - 1)]; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int s = s0 + 256 * k; if (s < S) l_s[s] = t[k]; }
-    }
-}
-
 // ---- wave per user (S <= 256) ---------------------------------------------------------------------------------
 // Samples sit in <= 4 registers per lane (sample s = r * 64 + lane), padded with -inf: v = (1 - y_p) + -inf never violates.  The
 // positives are loaded 64 per pass and taken in turn; everything per positive is wave-uniform: a compare and a ballot per register,
 // the first set bit, a popcount of the kept ballots up to it.  Lane q keeps positive q's result, so the pass ends in coalesced stores.
-// HITS: a row of <= 64 interactions is held in registers -- lane i column i (INT32_MAX beyond the row) and its pos_slot --
-// and searched with lane shuffles, a branchless six-step lower bound; longer rows take the binary search in memory.
+// HITS: a row of <= 64 interactions is held and searched in registers (HIT_ROW_LOAD / HIT_ROW_TEST); longer rows take the binary search in memory.
 template <bool HITS>
 __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ pos_slot, const float* __restrict__ pred,
@@ -69,33 +42,25 @@ __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
-    float ys[WP_WAVE_SR];
+    float ys[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < WP_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
-    uint64_t kept[WP_WAVE_SR];
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) ys[r] = (r * 64 + lane < S) ? samp[u * S + r * 64 + lane] : -INFINITY;
+    uint64_t kept[SAMPLED_WAVE_SR];
     if (HITS) {
-        const bool whole = e - b <= 64;                            // (wave-uniform)
-        int32_t col = 0x7fffffff, col_slot = -1;
-        if (whole && b + lane < e) {
-            col = h.x_item[b + lane];
-            col_slot = pos_slot[b + lane];
-        }
+        bool whole;                                                // (wave-uniform)
+        int32_t col, col_slot;
+        HIT_ROW_LOAD(whole, col, col_slot, true, h.x_item, pos_slot, b, e, lane);
 #pragma unroll
-        for (int r = 0; r < WP_WAVE_SR; ++r) {
+        for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
             kept[r] = 0ull;
             if (r * 64 >= S) continue;                             // (wave-uniform)
             const bool live = r * 64 + lane < S;
             const int32_t item = live ? h.samples[u * S + r * 64 + lane] : -1;
             bool hit;
             if (whole) {
-                int at_row = 0;                                    // columns [0, at_row) are below the item
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1)
-                    if (__shfl(col, at_row + step - 1, 64) < item) at_row += step;
-                const int32_t at_col = __shfl(col, at_row, 64), at_slot = __shfl(col_slot, at_row, 64);   // (both by every lane)
-                hit = wp_hit(at_col, at_slot, item);
+                HIT_ROW_TEST(hit, col, col_slot, item);
             } else {
-                hit = live && wp_is_hit(h.x_item, pos_slot, b, e, item);
+                hit = live && row_is_hit(h.x_item, pos_slot, b, e, item);
             }
             kept[r] = __builtin_amdgcn_ballot_w64(live && !hit);
         }
@@ -116,7 +81,7 @@ __global__ __launch_bounds__(256) void warp_fwd_wave_kernel(
             int32_t f = -1, n = 1, before = 0;
             float vf = 0.f;
 #pragma unroll
-            for (int r = 0; r < WP_WAVE_SR; ++r) {
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r) {
                 if (r * 64 >= S || f >= 0) continue;               // (wave-uniform)
                 const float v = base + ys[r];
                 uint64_t m = __builtin_amdgcn_ballot_w64(v > 0.f);
@@ -156,9 +121,9 @@ __global__ __launch_bounds__(256) void warp_bwd_wave_kernel(
     if (u >= n_users) return;
     const int lane = lane_id();
     const int64_t b = indptr[u], e = indptr[u + 1];
-    float acc[WP_WAVE_SR];
+    float acc[SAMPLED_WAVE_SR];
 #pragma unroll
-    for (int r = 0; r < WP_WAVE_SR; ++r) acc[r] = 0.f;
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r) acc[r] = 0.f;
     for (int64_t p0 = b; p0 < e; p0 += 64) {
         const int np = (int)((e - p0 < 64) ? (e - p0) : 64);
         int32_t f = -1;
@@ -176,12 +141,12 @@ __global__ __launch_bounds__(256) void warp_bwd_wave_kernel(
             const int32_t fq = __shfl(f, q, 64);
             const float cq = __shfl(c, q, 64);
 #pragma unroll
-            for (int r = 0; r < WP_WAVE_SR; ++r)
+            for (int r = 0; r < SAMPLED_WAVE_SR; ++r)
                 if ((fq >> 6) == r && (fq & 63) == lane) acc[r] += cq;
         }
     }
 #pragma unroll
-    for (int r = 0; r < WP_WAVE_SR; ++r)
+    for (int r = 0; r < SAMPLED_WAVE_SR; ++r)
         if (r * 64 + lane < S) d_samp[u * S + r * 64 + lane] = acc[r];
 }
 
@@ -202,11 +167,11 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(
     const int64_t b = indptr[u], e = indptr[u + 1];
     if (b == e) return;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    wp_fill_samples(l_s, samp, u, S);
+    fill_samples(l_s, samp, u, S);
     if (HITS) {
         for (int c = wave; c < n_chunks; c += 4) {
             const int s = c * 64 + lane;
-            const bool keep = s < S && !wp_is_hit(h.x_item, pos_slot, b, e, h.samples[u * S + (s < S ? s : S - 1)]);
+            const bool keep = s < S && !row_is_hit(h.x_item, pos_slot, b, e, h.samples[u * S + (s < S ? s : S - 1)]);
             const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
             if (lane == 0) l_kept[c] = m;
         }
@@ -282,25 +247,13 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(
 }
 
 // ---- entry points ------------------------------------------------------------------------------------------------
-// dynamic LDS above 64 KB (S close to 16384) has to be asked for
-template <typename K>
-static inline void allow_lds(K kernel, size_t lds)
-{
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-static inline bool use_wave_form(int32_t n_sampled)
-{
-    return n_sampled <= 64 * WP_WAVE_SR && trec_get_tuning("wmrb_wave", 1);
-}
-
 template <bool HITS>
 static void launch_fwd(const int64_t* indptr, const int32_t* pos_slot, const float* pred_serial, const float* sample_pred,
                        int64_t n_users, int32_t n_items_m1, int32_t n_sampled, float* loss, int32_t* first, float* weight, WpHits h,
                        hipStream_t stream)
 {
     if (use_wave_form(n_sampled)) {
-        hipLaunchKernelGGL(warp_fwd_wave_kernel<HITS>, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, stream, indptr,
+        hipLaunchKernelGGL(warp_fwd_wave_kernel<HITS>, wave_form_grid(n_users), dim3(256), 0, stream, indptr,
                            pos_slot, pred_serial, sample_pred, n_users, n_sampled, n_items_m1, loss, first, weight, h);
         return;
     }
@@ -341,7 +294,7 @@ extern "C" int trec_warp_bwd(const int64_t* indptr, const int32_t* pos_slot, con
     TREC_REQUIRE(n_sampled >= 1 && n_sampled <= 16384, "trec_warp_bwd: n_sampled must be in [1, 16384]");
     if (n_users == 0) return TREC_OK;
     if (use_wave_form(n_sampled))
-        hipLaunchKernelGGL(warp_bwd_wave_kernel, dim3((unsigned)ceil_div64(n_users * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(warp_bwd_wave_kernel, wave_form_grid(n_users), dim3(256), 0, (hipStream_t)stream,
                            indptr, pos_slot, first, weight, grad_loss, n_users, n_sampled, d_pred_serial, d_sample_pred);
     else
         hipLaunchKernelGGL(warp_bwd_kernel, dim3((unsigned)n_users), dim3(256), 0, (hipStream_t)stream, indptr, pos_slot, first,

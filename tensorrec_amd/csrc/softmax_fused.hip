@@ -18,34 +18,9 @@
 // in a fixed order (xor butterfly inside a wave, the four waves' partials added as (0 + 1) + (2 + 3)): a call is deterministic.
 // expf / logf are the library's (no fast-math): the error bars of tests/sampled_loss_reference.py apply as they stand.
 #include "user_fused_body.hpp"
+#include "sampled_common.hpp"   // hit_column, HIT_SCAN4, ssm_terms, logq_correction, the butterfly reductions, temperature_ok
 
 namespace {
-
-__device__ __forceinline__ float block_max(float v, float* red)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the per-positive terms from the user's (M, Z) (loss_sampled.hip's ssm_terms): bz = b Z, D = a + b Z
-__device__ __forceinline__ void positive_terms(float yp, float M, float Z, float t, float& m, float& b, float& bz, float& D)
-{
-    m = fmaxf(M, yp);
-    const float a = expf((yp - m) * t);
-    b = expf((M - m) * t);
-    bz = b * Z;
-    D = a + bz;
-}
 
 // ITERS, RMAX, SURE: as in wmrb_user_fused_kernel.  ADJ: the adjusted loss phase (use_q: the logQ correction, no_hits: accidental
 // hits leave the sums); the plain instantiations carry none of it -- no id reload, no log q gather, no hit test.
@@ -91,7 +66,7 @@ __global__ __launch_bounds__(256, (ITERS == 1 && RMAX == 16) ? 4 : 1) void softm
     // the columns a sample is tested against: the user's interactions with pos_slot >= 0, -1 (no item) for the others and
     // for the padding up to a multiple of four
     const int np4 = (n_pos + 3) & ~3;
-    if (ADJ && no_hits && tid < np4) l_xid[tid] = (my_slot >= 0) ? xi_ld : -1;
+    if (ADJ && no_hits && tid < np4) l_xid[tid] = hit_column(xi_ld, my_slot);
     __syncthreads();
 
     // ---- (c) loss terms and coefficients: thread s owns sample s, thread q interaction q ----
@@ -100,44 +75,41 @@ __global__ __launch_bounds__(256, (ITERS == 1 && RMAX == 16) ? 4 : 1) void softm
     const float yp = l_y[S + qi];
     float dp = 0.f, term = 0.f, cs = 0.f;
     if (!ADJ) {
-        const float M = block_max(ys, l_red);
+        const float M = wg_max_butterfly(ys, l_red);
         const float E = expf((ys - M) * t);
-        const float Z = block_sum(E, l_red + 4);
+        const float Z = wg_sum_butterfly(E, l_red + 4);
         if (my_slot >= 0) {
             float m, bb, bz, D;
-            positive_terms(yp, M, Z, t, m, bb, bz, D);
+            ssm_terms(yp, M, Z, t, m, bb, bz, D);
             loss[my_slot] = (m - yp) * t + logf(D);
             dp = -t * (bz / D);
             term = bb / D;
         }
-        const float K = block_sum(term, l_red + 8);              // a non-positive interaction or an idle thread adds an exact 0
+        const float K = wg_sum_butterfly(term, l_red + 8);              // a non-positive interaction or an idle thread adds an exact 0
         cs = (t * E) * K;
     } else {
         bool kept = is_sample;
         if (no_hits) {                                           // (uniform branch)
-            bool hit = false;
-            for (int q4 = 0; q4 < np4; q4 += 4) {                // LDS broadcast reads: every thread walks the same addresses
-                const int32_t c0 = l_xid[q4], c1 = l_xid[q4 + 1], c2 = l_xid[q4 + 2], c3 = l_xid[q4 + 3];
-                hit = hit || c0 == my_sample || c1 == my_sample || c2 == my_sample || c3 == my_sample;
-            }
+            bool hit;
+            HIT_SCAN4(hit, l_xid, np4, my_sample);
             kept = kept && !hit;
         }
-        const float c = (use_q && is_sample) ? -(log_s + l_lq[tid]) : 0.f;
-        const float Rm = block_max(kept ? ys : -INFINITY, l_red);
+        const float c = (use_q && is_sample) ? logq_correction(log_s, l_lq[tid]) : 0.f;
+        const float Rm = wg_max_butterfly(kept ? ys : -INFINITY, l_red);
         if (Rm != -INFINITY) {                                   // (uniform) -inf: every sample of this user is a hit
             const float w = kept ? (ys - Rm) * t + c : -INFINITY;
-            const float M = block_max(w, l_red + 4);
+            const float M = wg_max_butterfly(w, l_red + 4);
             const float E = expf(w - M);                          // 0 for a hit and for padding
-            const float Z = block_sum(E, l_red + 8);
+            const float Z = wg_sum_butterfly(E, l_red + 8);
             if (my_slot >= 0) {
                 const float wp = (yp - Rm) * t;
                 float m, bb, bz, D;
-                positive_terms(wp, M, Z, 1.0f, m, bb, bz, D);
+                ssm_terms(wp, M, Z, 1.0f, m, bb, bz, D);
                 loss[my_slot] = (m - wp) + logf(D);
                 dp = -t * (bz / D);
                 term = bb / D;
             }
-            const float K = block_sum(term, l_red + 12);
+            const float K = wg_sum_butterfly(term, l_red + 12);
             cs = kept ? (t * E) * K : 0.f;                        // a hit's coefficient is exactly 0
         } else if (my_slot >= 0) {
             loss[my_slot] = 0.f;
@@ -166,9 +138,7 @@ __global__ __launch_bounds__(256, (ITERS == 1 && RMAX == 16) ? 4 : 1) void softm
 // row <= 256 (128 for d > 128).
 extern "C" int trec_softmax_fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d)
 {
-    const int64_t r4 = covered_rows4(n_sampled, max_interactions_per_user, d);
-    if (r4 < 0) return -1;
-    return (int)((4 * r4 + 16 + 8 * (int64_t)d) * 4);
+    return fused_lds_bytes(n_sampled, max_interactions_per_user, d);
 }
 
 extern "C" int trec_softmax_fused_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
@@ -179,27 +149,16 @@ extern "C" int trec_softmax_fused_step(const float* U, const float* V, const flo
                                        float* pred_serial, float* dU, float* d_user_bias, float* coef_samples, float* coef_pairs,
                                        int32_t* sample_hist, int32_t* sample_rank, void* stream)
 {
-    TREC_REQUIRE(U && V && indptr && samples && loss && pred_serial && dU && coef_samples && coef_pairs,
-                 "trec_softmax_fused_step: null pointer");
-    TREC_REQUIRE(isfinite(inv_temperature) && inv_temperature > 0.f,
-                 "trec_softmax_fused_step: inv_temperature must be finite and > 0");
-    TREC_REQUIRE(!user_bias == !d_user_bias, "trec_softmax_fused_step: user_bias and d_user_bias go together");
-    TREC_REQUIRE(sample_hist || !sample_rank, "trec_softmax_fused_step: sample_rank needs sample_hist");
+    USER_FUSED_REQUIRE_POINTERS("trec_softmax_fused_step");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_fused_step: inv_temperature must be finite and > 0");
+    USER_FUSED_REQUIRE_PAIRS("trec_softmax_fused_step");
     TREC_REQUIRE(!log_q_correction || (n_items >= 1 && n_items < ((int64_t)1 << 31)),
                  "trec_softmax_fused_step: n_items must lie in [1, 2^31) with the logQ correction");
     TREC_REQUIRE(!remove_hits || (x_item && pos_slot), "trec_softmax_fused_step: remove_hits needs the interaction arrays");
-    const int lds = trec_softmax_fused_lds_bytes(n_sampled, max_interactions_per_user, d);
-    if (lds < 0) {
-        trec_set_last_error("trec_softmax_fused_step: configuration not covered (see trec_softmax_fused_lds_bytes)");
-        return TREC_ERR_UNSUPPORTED;
-    }
-    if (n_users == 0) return TREC_OK;
-    TREC_REQUIRE(max_interactions_per_user == 0 || (x_item && pos_slot), "trec_softmax_fused_step: null interaction arrays");
-    const int32_t max_rows = n_sampled + max_interactions_per_user;
+    USER_FUSED_COVERED("trec_softmax_fused_step", trec_softmax_fused_lds_bytes);
     const float log_s = (float)log((double)n_sampled);
     const int use_q = log_q_correction ? 1 : 0, no_hits = remove_hits ? 1 : 0;
     const bool adj = use_q || no_hits;
-    hipStream_t st = (hipStream_t)stream;
 #define TREC_FUSED_K(IT, RM, SU, ADJ)                                                                                          \
     hipLaunchKernelGGL((softmax_user_fused_kernel<IT, RM, SU, ADJ>), dim3((unsigned)n_users), dim3(256), lds, st, U, V,         \
                        user_bias, item_bias, indptr, x_item, pos_slot, samples, use_q ? log_q : (const float*)nullptr, n_users, \
@@ -210,24 +169,7 @@ extern "C" int trec_softmax_fused_step(const float* U, const float* V, const flo
         if (adj) TREC_FUSED_K(IT, RM, SU, true);                                                                               \
         else TREC_FUSED_K(IT, RM, SU, false);                                                                                  \
     } while (0)
-#ifdef TREC_WMRB_NO_EARLY
-    const int sure = 0;
-#else
-    const int sure = n_sampled / 8;                      // register rows r < sure hold samples in every subgroup (8 r + 7 < S)
-#endif
-    if (d <= 128 && max_rows <= 128) {
-        if (sure >= 12) TREC_FUSED(1, 16, 12);
-        else if (sure >= 8) TREC_FUSED(1, 16, 8);
-        else if (sure >= 4) TREC_FUSED(1, 16, 4);
-        else TREC_FUSED(1, 16, 0);
-    } else if (d <= 128) {
-        if (sure >= 16) TREC_FUSED(1, 32, 16);
-        else TREC_FUSED(1, 32, 0);
-    } else {
-        if (sure >= 8) TREC_FUSED(2, 16, 8);
-        else TREC_FUSED(2, 16, 0);
-    }
+    USER_FUSED_LAUNCH("trec_softmax_fused_step");
 #undef TREC_FUSED
 #undef TREC_FUSED_K
-    return trec_check_launch("trec_softmax_fused_step");
 }

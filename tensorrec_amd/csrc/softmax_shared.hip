@@ -16,7 +16,7 @@
 //             operations in the same order in all three roles, so it is the same float); partial [S, d] products and row sums per
 //             slice, added in slice order by reduce_slices_kernel.
 // Every sum has a fixed order and there are no float atomics: a call is deterministic.
-#include "common.hpp"
+#include "sampled_common.hpp"   // temperature_ok
 #include <math.h>
 
 #define SS_STATS 0
@@ -379,7 +379,6 @@ static int ss_dispatch(const SharedParams& p, int n_slices, hipStream_t st)
     return ss_launch<128, ROLE>(p, n_slices, st);
 }
 
-static bool ss_temperature_ok(float t) { return t > 0.f && t < INFINITY; }
 
 extern "C" int trec_softmax_shared_stats(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
                                          const float* sample_c, int64_t n_users, int32_t n_sampled, int32_t d,
@@ -388,7 +387,7 @@ extern "C" int trec_softmax_shared_stats(const float* U, const float* Vs, const 
     TREC_REQUIRE(U && Vs && M && Z, "trec_softmax_shared_stats: null pointer");
     TREC_REQUIRE(n_sampled >= 1, "trec_softmax_shared_stats: n_sampled must be >= 1");
     TREC_REQUIRE(ss_shape_ok(n_sampled, d), "trec_softmax_shared_stats: need d % 4 == 0 and 4 <= d <= 128");
-    TREC_REQUIRE(ss_temperature_ok(inv_temperature), "trec_softmax_shared_stats: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_shared_stats: inv_temperature must be finite and > 0");
     TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_shared_stats: n_users must fit int32");
     if (n_users == 0) return TREC_OK;
     SharedParams p = {};
@@ -405,7 +404,7 @@ extern "C" int trec_softmax_shared_positives(const int64_t* indptr, const int32_
                                              float* tK, float* d_user_bias, void* stream)
 {
     TREC_REQUIRE(indptr && M && Z && tK, "trec_softmax_shared_positives: null pointer");
-    TREC_REQUIRE(ss_temperature_ok(inv_temperature), "trec_softmax_shared_positives: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_shared_positives: inv_temperature must be finite and > 0");
     TREC_REQUIRE(n_users >= 0, "trec_softmax_shared_positives: n_users must be >= 0");
     if (n_users == 0) return TREC_OK;
     hipLaunchKernelGGL(shared_positives_kernel, dim3((unsigned)ceil_div64(n_users, 256)), dim3(256), 0, (hipStream_t)stream, indptr,
@@ -421,7 +420,7 @@ extern "C" int trec_softmax_shared_grads(const float* U, const float* Vs, const 
     TREC_REQUIRE(U && Vs && M && tK && dU && dVs, "trec_softmax_shared_grads: null pointer");
     TREC_REQUIRE(n_sampled >= 1, "trec_softmax_shared_grads: n_sampled must be >= 1");
     TREC_REQUIRE(ss_shape_ok(n_sampled, d), "trec_softmax_shared_grads: need d % 4 == 0 and 4 <= d <= 128");
-    TREC_REQUIRE(ss_temperature_ok(inv_temperature), "trec_softmax_shared_grads: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_shared_grads: inv_temperature must be finite and > 0");
     TREC_REQUIRE(n_users >= 1 && n_users < ((int64_t)1 << 31), "trec_softmax_shared_grads: n_users must lie in [1, 2^31)");
     TREC_REQUIRE(n_slices == trec_softmax_shared_slices(n_users, n_sampled, d),
                  "trec_softmax_shared_grads: n_slices must be trec_softmax_shared_slices' answer");
@@ -469,7 +468,7 @@ extern "C" int trec_softmax_full_positives(const int64_t* indptr, const int32_t*
                                            float* tK, float* d_user_bias, void* stream)
 {
     TREC_REQUIRE(indptr && M && Z && tK, "trec_softmax_full_positives: null pointer");
-    TREC_REQUIRE(ss_temperature_ok(inv_temperature), "trec_softmax_full_positives: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_full_positives: inv_temperature must be finite and > 0");
     TREC_REQUIRE(n_users >= 0, "trec_softmax_full_positives: n_users must be >= 0");
     if (n_users == 0) return TREC_OK;
     hipLaunchKernelGGL(full_positives_kernel, dim3((unsigned)ceil_div64(n_users, 256)), dim3(256), 0, (hipStream_t)stream, indptr,

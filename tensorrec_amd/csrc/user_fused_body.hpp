@@ -1,5 +1,6 @@
-// tensorrec_amd/csrc/user_fused_body.hpp -- what the one-pass per-user training steps share, as TEXT: csrc/wmrb_fused.hip and
-// csrc/softmax_fused.hip include it once at file scope for the helpers and three times inside their kernel
+// tensorrec_amd/csrc/user_fused_body.hpp -- what the one-pass per-user training steps share, as TEXT: csrc/wmrb_fused.hip,
+// csrc/softmax_fused.hip and csrc/warp_fused.hip include it once at file scope for the helpers and the host section (the entry
+// checks, the coverage and the instantiation ladder of their entry points) and three times inside their kernel
 // (template <int ITERS, int RMAX, int SURE, ...>), each time with one USER_FUSED_PART defined:
 //     USER_FUSED_PART 1   the prologue: thread indices, the sample ids, the user's interaction range, the user without interactions
 //     USER_FUSED_PART 2   phases (a), (b): the user's row and its R = S + n_pos item rows into registers, predictions into l_y (and
@@ -64,7 +65,60 @@ static int64_t covered_rows4(int32_t n_sampled, int32_t max_interactions_per_use
     return (rows + 3) & ~(int64_t)3;
 }
 
+// dynamic LDS of the softmax and WARP steps (one layout: four arrays of rows4, 16 words of reductions / kept mask, partial dU [8][d])
+static int fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d)
+{
+    const int64_t r4 = covered_rows4(n_sampled, max_interactions_per_user, d);
+    return r4 < 0 ? -1 : (int)((4 * r4 + 16 + 8 * (int64_t)d) * 4);
+}
+
 }  // namespace
+
+// ---- host: what the entry points trec_<loss>_fused_step share, as macros over the parameter names all three use.  An entry point is
+//     USER_FUSED_REQUIRE_POINTERS(name);  USER_FUSED_REQUIRE_PAIRS(name);  its own TREC_REQUIREs, in the order it always had them (the
+//     softmax step's temperature check stands between the two);  USER_FUSED_COVERED(name, lds_bytes);  its constants and
+//     #define TREC_FUSED(IT, RM, SU) <launch of that instantiation>;  USER_FUSED_LAUNCH(name);  #undef TREC_FUSED
+#define USER_FUSED_REQUIRE_POINTERS(name) \
+    TREC_REQUIRE(U && V && indptr && samples && loss && pred_serial && dU && coef_samples && coef_pairs, name ": null pointer")
+#define USER_FUSED_REQUIRE_PAIRS(name)                                                                                         \
+    TREC_REQUIRE(!user_bias == !d_user_bias, name ": user_bias and d_user_bias go together");                                  \
+    TREC_REQUIRE(sample_hist || !sample_rank, name ": sample_rank needs sample_hist")
+
+// defines lds, max_rows and st; leaves with TREC_ERR_UNSUPPORTED where the shape is not covered (the host then runs the generic step)
+#define USER_FUSED_COVERED(name, lds_bytes)                                                                                    \
+    const int lds = lds_bytes(n_sampled, max_interactions_per_user, d);                                                        \
+    if (lds < 0) {                                                                                                             \
+        trec_set_last_error(name ": configuration not covered (see " #lds_bytes ")");                                          \
+        return TREC_ERR_UNSUPPORTED;                                                                                           \
+    }                                                                                                                          \
+    if (n_users == 0) return TREC_OK;                                                                                          \
+    TREC_REQUIRE(max_interactions_per_user == 0 || (x_item && pos_slot), name ": null interaction arrays");                    \
+    const int32_t max_rows = n_sampled + max_interactions_per_user;                                                            \
+    hipStream_t st = (hipStream_t)stream
+
+// register rows r < sure hold samples in every subgroup (8 r + 7 < S)
+#ifdef TREC_WMRB_NO_EARLY
+#define USER_FUSED_SURE(n_sampled) 0
+#else
+#define USER_FUSED_SURE(n_sampled) ((n_sampled) / 8)
+#endif
+
+// the <ITERS, RMAX, SURE> instantiations (tests/softmax_step_reference.py mirrors this ladder)
+#define USER_FUSED_LAUNCH(name)                                                                                                \
+    const int sure = USER_FUSED_SURE(n_sampled);                                                                               \
+    if (d <= 128 && max_rows <= 128) {                                                                                         \
+        if (sure >= 12) TREC_FUSED(1, 16, 12);                                                                                 \
+        else if (sure >= 8) TREC_FUSED(1, 16, 8);                                                                              \
+        else if (sure >= 4) TREC_FUSED(1, 16, 4);                                                                              \
+        else TREC_FUSED(1, 16, 0);                                                                                             \
+    } else if (d <= 128) {                                                                                                     \
+        if (sure >= 16) TREC_FUSED(1, 32, 16);                                                                                 \
+        else TREC_FUSED(1, 32, 0);                                                                                             \
+    } else {                                                                                                                   \
+        if (sure >= 8) TREC_FUSED(2, 16, 8);                                                                                   \
+        else TREC_FUSED(2, 16, 0);                                                                                             \
+    }                                                                                                                          \
+    return trec_check_launch(name)
 
 #elif USER_FUSED_PART == 1
     const int64_t u = blockIdx.x;

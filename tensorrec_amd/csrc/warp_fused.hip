@@ -60,17 +60,14 @@ __global__ __launch_bounds__(256, (ITERS == 1 && RMAX == 16) ? 4 : 1) void warp_
     // the columns a sample is tested against: the user's interactions with pos_slot >= 0, -1 (no item) for the others and
     // for the padding up to a multiple of four
     const int np4 = (n_pos + 3) & ~3;
-    if (HITS && tid < np4) l_xid[tid] = wp_hit_column(xi_ld, my_slot);
+    if (HITS && tid < np4) l_xid[tid] = hit_column(xi_ld, my_slot);
     __syncthreads();
 
     // ---- (c) loss terms and coefficients: thread s owns sample s, thread q interaction q ----
     const bool is_sample = tid < S;
     if (HITS) {
-        bool hit = false;
-        for (int q4 = 0; q4 < np4; q4 += 4) {                    // LDS broadcast reads: every thread walks the same addresses
-            const int32_t c0 = l_xid[q4], c1 = l_xid[q4 + 1], c2 = l_xid[q4 + 2], c3 = l_xid[q4 + 3];
-            hit = hit || c0 == my_sample || c1 == my_sample || c2 == my_sample || c3 == my_sample;
-        }
+        bool hit;
+        HIT_SCAN4(hit, l_xid, np4, my_sample);
         const uint64_t m = __builtin_amdgcn_ballot_w64(is_sample && !hit);       // the kept samples 64 wave .. 64 wave + 63
         if (lane == 0) l_kept[wave] = m;
         __syncthreads();
@@ -140,9 +137,7 @@ __global__ __launch_bounds__(256, (ITERS == 1 && RMAX == 16) ? 4 : 1) void warp_
 // longest interaction row <= 256 (128 for d > 128).
 extern "C" int trec_warp_fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d)
 {
-    const int64_t r4 = covered_rows4(n_sampled, max_interactions_per_user, d);
-    if (r4 < 0) return -1;
-    return (int)((4 * r4 + 16 + 8 * (int64_t)d) * 4);
+    return fused_lds_bytes(n_sampled, max_interactions_per_user, d);
 }
 
 extern "C" int trec_warp_fused_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
@@ -152,22 +147,12 @@ extern "C" int trec_warp_fused_step(const float* U, const float* V, const float*
                                     float* dU, float* d_user_bias, float* coef_samples, float* coef_pairs, int32_t* first,
                                     int32_t* sample_hist, int32_t* sample_rank, void* stream)
 {
-    TREC_REQUIRE(U && V && indptr && samples && loss && pred_serial && dU && coef_samples && coef_pairs,
-                 "trec_warp_fused_step: null pointer");
-    TREC_REQUIRE(!user_bias == !d_user_bias, "trec_warp_fused_step: user_bias and d_user_bias go together");
-    TREC_REQUIRE(sample_hist || !sample_rank, "trec_warp_fused_step: sample_rank needs sample_hist");
+    USER_FUSED_REQUIRE_POINTERS("trec_warp_fused_step");
+    USER_FUSED_REQUIRE_PAIRS("trec_warp_fused_step");
     TREC_REQUIRE(n_items >= 1 && n_items < ((int64_t)1 << 31), "trec_warp_fused_step: n_items must lie in [1, 2^31)");
     TREC_REQUIRE(!remove_hits || (x_item && pos_slot), "trec_warp_fused_step: remove_hits needs the interaction arrays");
-    const int lds = trec_warp_fused_lds_bytes(n_sampled, max_interactions_per_user, d);
-    if (lds < 0) {
-        trec_set_last_error("trec_warp_fused_step: configuration not covered (see trec_warp_fused_lds_bytes)");
-        return TREC_ERR_UNSUPPORTED;
-    }
-    if (n_users == 0) return TREC_OK;
-    TREC_REQUIRE(max_interactions_per_user == 0 || (x_item && pos_slot), "trec_warp_fused_step: null interaction arrays");
-    const int32_t max_rows = n_sampled + max_interactions_per_user;
+    USER_FUSED_COVERED("trec_warp_fused_step", trec_warp_fused_lds_bytes);
     const int32_t n_items_m1 = (int32_t)(n_items - 1);
-    hipStream_t st = (hipStream_t)stream;
 #define TREC_FUSED_K(IT, RM, SU, HITS)                                                                                         \
     hipLaunchKernelGGL((warp_user_fused_kernel<IT, RM, SU, HITS>), dim3((unsigned)n_users), dim3(256), lds, st, U, V, user_bias, \
                        item_bias, indptr, x_item, pos_slot, samples, n_users, n_sampled, d, n_items_m1, max_rows, loss,        \
@@ -177,24 +162,7 @@ extern "C" int trec_warp_fused_step(const float* U, const float* V, const float*
         if (remove_hits) TREC_FUSED_K(IT, RM, SU, true);                                                                       \
         else TREC_FUSED_K(IT, RM, SU, false);                                                                                  \
     } while (0)
-#ifdef TREC_WMRB_NO_EARLY
-    const int sure = 0;
-#else
-    const int sure = n_sampled / 8;                      // register rows r < sure hold samples in every subgroup (8 r + 7 < S)
-#endif
-    if (d <= 128 && max_rows <= 128) {
-        if (sure >= 12) TREC_FUSED(1, 16, 12);
-        else if (sure >= 8) TREC_FUSED(1, 16, 8);
-        else if (sure >= 4) TREC_FUSED(1, 16, 4);
-        else TREC_FUSED(1, 16, 0);
-    } else if (d <= 128) {
-        if (sure >= 16) TREC_FUSED(1, 32, 16);
-        else TREC_FUSED(1, 32, 0);
-    } else {
-        if (sure >= 8) TREC_FUSED(2, 16, 8);
-        else TREC_FUSED(2, 16, 0);
-    }
+    USER_FUSED_LAUNCH("trec_warp_fused_step");
 #undef TREC_FUSED
 #undef TREC_FUSED_K
-    return trec_check_launch("trec_warp_fused_step");
 }

@@ -145,20 +145,10 @@ extern "C" int trec_wmrb_fused_step(const float* U, const float* V, const float*
                                     float* pred_serial, float* dU, float* d_user_bias, float* coef_samples,
                                     float* coef_pairs, int32_t* sample_hist, int32_t* sample_rank, void* stream)
 {
-    TREC_REQUIRE(U && V && indptr && samples && loss && pred_serial && dU && coef_samples && coef_pairs,
-                 "trec_wmrb_fused_step: null pointer");
-    TREC_REQUIRE(!user_bias == !d_user_bias, "trec_wmrb_fused_step: user_bias and d_user_bias go together");
-    TREC_REQUIRE(sample_hist || !sample_rank, "trec_wmrb_fused_step: sample_rank needs sample_hist");
-    const int lds = trec_wmrb_fused_lds_bytes(n_sampled, max_interactions_per_user, d);
-    if (lds < 0) {
-        trec_set_last_error("trec_wmrb_fused_step: configuration not covered (see trec_wmrb_fused_lds_bytes)");
-        return TREC_ERR_UNSUPPORTED;
-    }
-    if (n_users == 0) return TREC_OK;
-    TREC_REQUIRE(max_interactions_per_user == 0 || (x_item && pos_slot), "trec_wmrb_fused_step: null interaction arrays");
+    USER_FUSED_REQUIRE_POINTERS("trec_wmrb_fused_step");
+    USER_FUSED_REQUIRE_PAIRS("trec_wmrb_fused_step");
+    USER_FUSED_COVERED("trec_wmrb_fused_step", trec_wmrb_fused_lds_bytes);
     const float ratio = (float)n_items / (float)n_sampled;
-    const int32_t max_rows = n_sampled + max_interactions_per_user;
-    hipStream_t st = (hipStream_t)stream;
 #ifdef TREC_WMRB_ABLATE
     const int ablate = trec_get_tuning("wmrb_ablate", 0);
 #else
@@ -168,23 +158,6 @@ extern "C" int trec_wmrb_fused_step(const float* U, const float* V, const float*
     hipLaunchKernelGGL((wmrb_user_fused_kernel<IT, RM, SU>), dim3((unsigned)n_users), dim3(256), lds, st, U, V, user_bias,  \
                        item_bias, indptr, x_item, pos_slot, pos_weight, samples, n_users, n_sampled, d, ratio, max_rows, \
                        loss, pred_serial, dU, d_user_bias, coef_samples, coef_pairs, sample_hist, sample_rank, ablate)
-#ifdef TREC_WMRB_NO_EARLY
-    const int sure = 0;
-#else
-    const int sure = n_sampled / 8;                      // register rows r < sure hold samples in every subgroup (8 r + 7 < S)
-#endif
-    if (d <= 128 && max_rows <= 128) {
-        if (sure >= 12) TREC_FUSED(1, 16, 12);
-        else if (sure >= 8) TREC_FUSED(1, 16, 8);
-        else if (sure >= 4) TREC_FUSED(1, 16, 4);
-        else TREC_FUSED(1, 16, 0);
-    } else if (d <= 128) {
-        if (sure >= 16) TREC_FUSED(1, 32, 16);
-        else TREC_FUSED(1, 32, 0);
-    } else {
-        if (sure >= 8) TREC_FUSED(2, 16, 8);
-        else TREC_FUSED(2, 16, 0);
-    }
+    USER_FUSED_LAUNCH("trec_wmrb_fused_step");
 #undef TREC_FUSED
-    return trec_check_launch("trec_wmrb_fused_step");
 }

@@ -939,9 +939,13 @@ def _checked_log_q(sample_log_q, n_items):
     return _f32c(sample_log_q).reshape(-1)
 
 
-def _fused_step_buffers(u, ub, interactions, samples):
-    """What both per-user fused steps allocate: (loss [P+], pred [P], d_u, d_ub or None, coef_s [U, S], coef_p [P], the int32 sample
-    table, the same flattened, _fused_sample_grouping's triple)."""
+def _fused_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples):
+    """What the per-user fused steps start from: the [n_users, n_sampled] table checked, then (u, v, ub, ib) of _step_operands and what
+    all three allocate: (loss [P+], pred [P], d_u, d_ub or None, coef_s [U, S], coef_p [P], the int32 sample table, the same flattened,
+    _fused_sample_grouping's triple)."""
+    if samples.dim() != 2 or samples.shape[0] != interactions.shape[0]:
+        raise ValueError("samples must be an [n_users, n_sampled] table")
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
     S, dev, nnz = int(samples.shape[1]), u.device, interactions.nnz
     loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
@@ -952,7 +956,7 @@ def _fused_step_buffers(u, ub, interactions, samples):
     coef_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
     samples = samples.to(torch.int32).contiguous()
     xs = samples.reshape(-1)
-    return loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, _fused_sample_grouping(xs, n_users, n_items, S, dev)
+    return u, v, ub, ib, loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, _fused_sample_grouping(xs, n_users, n_items, S, dev)
 
 
 def _fused_sample_grouping(xs, n_users, n_items, S, dev):
@@ -971,6 +975,24 @@ def _fused_sample_grouping(xs, n_users, n_items, S, dev):
     return binned_bytes, ws32, ranks
 
 
+def _gather_over_items(interactions, coef, u, d_ib, accumulate=False, out=None):
+    """d item_in's share of the interactions (nnz >= 1): the per-pair coefficients ``coef`` gathered over the transposed interactions
+    (K1), with the row-sum epilogue -- epilogue 3 of K1: d b_i = the per-item sums into ``d_ib`` come out of the same pass -- where
+    there is an item bias (d_ib is not None); rows of popular items, above SPLIT_T, are summed as chunks."""
+    n_items, nnz = interactions.shape[1], interactions.nnz
+    indptr_t, users_t, perm_t = interactions.transposed()
+    if interactions.max_col_nnz > SPLIT_T:
+        return spmm_split(indptr_t, users_t, coef, perm_t, n_items, nnz, u, accumulate=accumulate, out=out, want_rowsum=d_ib)
+    return _spmm_rowsum(indptr_t, users_t, coef, perm_t, n_items, nnz, u, EPI_ROWSUM if d_ib is not None else EPI_NONE, accumulate, out,
+                        d_ib)
+
+
+def _gather_over_users(interactions, coef, v):
+    """d user_in's share of the interactions (nnz >= 1): ``coef`` gathered over the interactions (K1), chunked above SPLIT_T."""
+    gather = spmm_split if interactions.max_row_nnz > SPLIT_T else spmm_raw
+    return gather(interactions.indptr, interactions.x_item32, coef, None, interactions.shape[0], interactions.nnz, v)
+
+
 def _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks):
     """The item side of a one-pass fused step (wmrb_fused_step, softmax_fused_step, warp_fused_step): d item_in = G^T . user_in over both pair lists,
     d b_i = per-item sums of the coefficients -- the static transposed structure for the interactions, the binned or ranked grouping
@@ -985,15 +1007,9 @@ def _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned
     # slows down by exactly what it hides)
     d_v = torch.zeros_like(v) if nnz == 0 else None
     d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
-    # (epilogue 3 of K1: the row sums of the gathered coefficients = d b_i come out of the same pass)
     epi = EPI_ROWSUM if ib is not None else EPI_NONE
-    rowsum = d_ib if epi == EPI_ROWSUM else None
     if nnz:
-        indptr_t, users_t, perm_t = interactions.transposed()
-        if interactions.max_col_nnz > SPLIT_T:           # popular items: their pairs are summed as chunks
-            d_v = spmm_split(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, want_rowsum=rowsum)
-        else:
-            d_v = _spmm_rowsum(indptr_t, users_t, coef_p, perm_t, n_items, nnz, u, epi, False, None, d_ib)
+        d_v = _gather_over_items(interactions, coef_p, u, d_ib)
     split_samples = xs.numel() > n_items * _SPLIT_MEAN
     if binned_bytes > 0:
         ind_s = torch.empty((n_items + 1,), dtype=torch.int64, device=dev)
@@ -1018,12 +1034,12 @@ def _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned
         LAST_FUSED_STATS["sampled_pairs_with_coefficient_0"] = (coef_s == 0).sum()
         LAST_FUSED_STATS["loss_mean"] = loss.mean()
     if split_samples:                                    # few items: every bucket of samples is long
-        spmm_split(ind_s, None, None, None, n_items, xs.numel(), u, accumulate=True, out=d_v, want_rowsum=rowsum,
+        spmm_split(ind_s, None, None, None, n_items, xs.numel(), u, accumulate=True, out=d_v, want_rowsum=d_ib,
                    packed=entries)
     else:
         with _timed("spmm_csr"):
             N.call("trec_spmm_csr_packed", N.ptr(ind_s), N.ptr(entries), n_items, N.ptr(u), d, epi, 1, N.ptr(d_v),
-                   N.ptr(rowsum))
+                   N.ptr(d_ib))
     return d_v, d_ib
 
 
@@ -1033,10 +1049,10 @@ def wmrb_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
     The user side -- predictions of the interactions and of the sampled pairs, loss, dU, d b_u -- is one kernel with
     every item row gathered once; the item side groups the per-pair coefficients by item (static transposed structure
     for the interactions, device counting sort for the samples) and runs the segmented K1 gathers / segment sums."""
-    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
+    u, v, ub, ib, loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = \
+        _fused_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples)
     n_users, n_items = interactions.shape
     S, d = int(samples.shape[1]), u.shape[1]
-    loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = _fused_step_buffers(u, ub, interactions, samples)
     weight = interactions.balanced_weight() if balanced else None
     with _timed("wmrb_fused_step"):
         N.call("trec_wmrb_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
@@ -1058,13 +1074,11 @@ def softmax_fused_step(user_in, item_in, user_bias, item_bias, interactions, sam
     sampled_softmax_loss (``temperature``, ``sample_log_q``, ``log_q_correction``, ``remove_accidental_hits`` as there).  Returns
     (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias); the item side is wmrb_fused_step's."""
     temperature = _checked_temperature(temperature)
-    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
+    u, v, ub, ib, loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = \
+        _fused_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples)
     n_users, n_items = interactions.shape
-    if tuple(samples.shape[:1]) != (n_users,) or samples.dim() != 2:
-        raise ValueError("samples must be an [n_users, n_sampled] table")
     S, d = int(samples.shape[1]), u.shape[1]
     log_q = _checked_log_q(sample_log_q, n_items) if log_q_correction and sample_log_q is not None else None
-    loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = _fused_step_buffers(u, ub, interactions, samples)
     with _timed("softmax_fused_step"):
         N.call("trec_softmax_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
                N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(samples), n_users, n_items, S, d,
@@ -1089,12 +1103,10 @@ def warp_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
     d user_bias, d item_bias), and with ``return_first`` the int32 [P] first violator of every interaction (-1: none) behind them;
     the item side is wmrb_fused_step's.  A positive moves ONE sample slot: at least S - n_u of a user's S sample coefficients are
     exact zeros, which the binned grouping drops from the item-side gather."""
-    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
+    u, v, ub, ib, loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = \
+        _fused_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples)
     n_users, n_items = interactions.shape
-    if tuple(samples.shape[:1]) != (n_users,) or samples.dim() != 2:
-        raise ValueError("samples must be an [n_users, n_sampled] table")
     S, d = int(samples.shape[1]), u.shape[1]
-    loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = _fused_step_buffers(u, ub, interactions, samples)
     first = torch.empty((interactions.nnz,), dtype=torch.int32, device=u.device) if return_first else None
     with _timed("warp_fused_step"):
         N.call("trec_warp_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
@@ -1119,6 +1131,30 @@ def _f32r(x):
 def softmax_shared_supported(n_sampled, interactions, d):
     """Can the shared-negatives MFMA step (csrc/softmax_shared.hip) run this shape, and is tuning ``softmax_shared`` on?"""
     return _step_supported("softmax_shared", n_sampled, interactions, d)
+
+
+def _streamed_softmax_positives(name, u, vs, ub, bs, cs, v, ib, interactions, inv_t):
+    """What the two streamed softmax steps (``name``: "softmax_shared", "softmax_full") share up to the tiles' gradients: the row
+    statistics of the streamed [S, d] operand (vs, bs, cs), then the positives -- K3 scores, the loss and d y_p per interaction, K_u
+    per user -- and their gradient over the users on K1's route.  Returns (loss, pred, d_pred, stat_m, t_k, d_u, d_ub)."""
+    n_users, S, d, dev, nnz = interactions.shape[0], int(vs.shape[0]), int(u.shape[1]), u.device, interactions.nnz
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    with _timed(name + "_stats"):
+        N.call("trec_softmax_shared_stats", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), n_users, S, d, inv_t,
+               N.ptr(stat_m), N.ptr(stat_z))
+    if nnz:
+        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
+               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
+    N.call("trec_%s_positives" % name, N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
+           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
+    d_u = _gather_over_users(interactions, d_pred, v) if nnz else torch.zeros_like(u)
+    return loss, pred, d_pred, stat_m, t_k, d_u, d_ub
 
 
 def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
@@ -1147,38 +1183,11 @@ def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, sa
             cs = -(_checked_log_q(sample_log_q, n_items).index_select(0, ids) + _f32r(math.log(S)))
         else:
             cs = torch.full((S,), -_f32r(_f32r(math.log(S)) + _f32r(-math.log(n_items))), dtype=torch.float32, device=dev)
-    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
-    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
     d_vs = torch.empty((S, d), dtype=torch.float32, device=dev)
     d_bs = torch.empty((S,), dtype=torch.float32, device=dev) if ib is not None else None
-    with _timed("softmax_shared_stats"):
-        N.call("trec_softmax_shared_stats", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), n_users, S, d, inv_t,
-               N.ptr(stat_m), N.ptr(stat_z))
-    # ---- the positives: K3 scores, the loss and d y_p per interaction, K_u per user; their gradients on K3's backward routes
-    if nnz:
-        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
-               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
-    N.call("trec_softmax_shared_positives", N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
-           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
+    loss, pred, d_pred, stat_m, t_k, d_u, d_ub = _streamed_softmax_positives("softmax_shared", u, vs, ub, bs, cs, v, ib, interactions, inv_t)
     d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
-    if nnz:
-        if interactions.max_row_nnz > SPLIT_T:
-            d_u = spmm_split(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
-        else:
-            d_u = spmm_raw(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
-        indptr_t, users_t, perm_t = interactions.transposed()
-        epi = EPI_ROWSUM if ib is not None else EPI_NONE
-        if interactions.max_col_nnz > SPLIT_T:
-            d_v = spmm_split(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, want_rowsum=d_ib if ib is not None else None)
-        else:
-            d_v = _spmm_rowsum(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, epi, False, None, d_ib)
-    else:
-        d_u, d_v = torch.zeros_like(u), torch.zeros_like(v)
+    d_v = _gather_over_items(interactions, d_pred, u, d_ib) if nnz else torch.zeros_like(v)
     # ---- the samples: dU += P . Vs, dVs = P^T . U in slices of the users, d b_s = the row sums
     n_slices = int(N.query("trec_softmax_shared_slices", n_users, S, d))
     ws = torch.empty((n_slices * S * (d + 1),), dtype=torch.float32, device=dev) if n_slices > 1 else None
@@ -1209,32 +1218,11 @@ def softmax_full_step(user_in, item_in, user_bias, item_bias, interactions, temp
     if not step_covers("softmax_shared", n_items, 0, d):
         raise ValueError("softmax_full_step covers d %% 4 == 0, 4 <= d <= %d; got d = %d" % (SOFTMAX_SHARED_MAX_D, d))
     inv_t = 1.0 / temperature
-    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
-    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
-    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
-    with _timed("softmax_full_stats"):
-        N.call("trec_softmax_shared_stats", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), None, n_users, n_items, d, inv_t,
-               N.ptr(stat_m), N.ptr(stat_z))
-    if nnz:
-        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
-               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
-    N.call("trec_softmax_full_positives", N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
-           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
     # The tile kernel's DU role ADDS to d user_in and its DV role OVERWRITES d item_in / d item_bias.  So the positives' K1 gather
     # over the users runs BEFORE the tiles (it writes d_u, the tiles add the softmax's share onto it) and their K1 gather over the
     # items runs AFTER them, accumulating (it adds -t u_u per positive, and -t per positive through the row-sum epilogue, onto what
     # the tiles wrote): no buffer is zeroed, every cell has one writer at a time, the order of every sum is fixed.
-    if nnz:
-        if interactions.max_row_nnz > SPLIT_T:
-            d_u = spmm_split(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
-        else:
-            d_u = spmm_raw(interactions.indptr, interactions.x_item32, d_pred, None, n_users, nnz, v)
-    else:
-        d_u = torch.zeros_like(u)
+    loss, pred, d_pred, stat_m, t_k, d_u, d_ub = _streamed_softmax_positives("softmax_full", u, v, ub, ib, None, v, ib, interactions, inv_t)
     d_v = torch.empty_like(v)
     d_ib = torch.empty((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
     n_slices = int(N.query("trec_softmax_shared_slices", n_users, n_items, d))
@@ -1243,13 +1231,7 @@ def softmax_full_step(user_in, item_in, user_bias, item_bias, interactions, temp
         N.call("trec_softmax_shared_grads", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), None, N.ptr(stat_m), N.ptr(t_k), n_users,
                n_items, d, inv_t, n_slices, N.ptr(ws), N.ptr(d_u), N.ptr(d_v), N.ptr(d_ib))
     if nnz:
-        indptr_t, users_t, perm_t = interactions.transposed()
-        if interactions.max_col_nnz > SPLIT_T:
-            spmm_split(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, accumulate=True, out=d_v,
-                       want_rowsum=d_ib if ib is not None else False)
-        else:
-            _spmm_rowsum(indptr_t, users_t, d_pred, perm_t, n_items, nnz, u, EPI_ROWSUM if ib is not None else EPI_NONE, True, d_v,
-                         d_ib)
+        _gather_over_items(interactions, d_pred, u, d_ib, accumulate=True, out=d_v)
     return loss, pred, d_u, d_v, d_ub, d_ib
 
 

@@ -47,7 +47,7 @@ def rows_capacity(d):
 
 
 def instantiation(S, max_pos, d):
-    """<ITERS, RMAX, SURE> of softmax_user_fused_kernel (the dispatch at the end of softmax_fused.hip), None where
+    """<ITERS, RMAX, SURE> of softmax_user_fused_kernel (the dispatch USER_FUSED_LAUNCH of csrc/user_fused_body.hpp), None where
     trec_softmax_fused_lds_bytes is -1"""
     if S < 1 or S > 256 or d < 4 or d % 4 or d > 256 or max_pos < 0 or S + max_pos > rows_capacity(d):
         return None

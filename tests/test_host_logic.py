@@ -409,3 +409,20 @@ def test_euclidean_candidate_counts_by_k():
     assert ops.EUCLID_WIDE_K_MAX <= ops.WIDE_K_MAX and ops.CASCADE_MAX_CHUNKS >= 64
     with pytest.raises(ValueError):
         ops.euclid_candidates_for(ops.EUCLID_WIDE_K_MAX + 1)
+
+
+def test_fused_steps_check_the_sample_table_before_any_native_call():
+    """All three per-user one-pass steps refuse a sample table whose first dimension is not n_users (ops._fused_step_buffers), on the
+    host: the kernels index it as [n_users, n_sampled] and a shorter one would be read out of bounds."""
+    import torch
+    from types import SimpleNamespace
+    from tensorrec_amd import ops
+    interactions = SimpleNamespace(shape=(5, 7))
+    u, v = torch.zeros((5, 4)), torch.zeros((7, 4))
+    for samples in (torch.zeros((4, 3), dtype=torch.int32), torch.zeros((15,), dtype=torch.int32)):
+        with pytest.raises(ValueError, match="n_users, n_sampled"):
+            ops.wmrb_fused_step(u, v, None, None, interactions, samples)
+        with pytest.raises(ValueError, match="n_users, n_sampled"):
+            ops.softmax_fused_step(u, v, None, None, interactions, samples, 1.0)
+        with pytest.raises(ValueError, match="n_users, n_sampled"):
+            ops.warp_fused_step(u, v, None, None, interactions, samples)
