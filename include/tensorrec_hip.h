@@ -235,7 +235,10 @@ int trec_score_prep_filter(const float* repr, int64_t n, int32_t d, int32_t kpad
  *       ||y|| + ||dy||, max ||dy||, max |bias - a b_s bias_q| / a (the bias quantisation error per unit of user scale a)};
  *       with a bias also side 2 (users first).
  *     side 2: bias_q = rint(bias / (scales[0] b_s)), sb_stats[s][3] and gstats[2] = max |bias| (both zeroed by the caller)
- *       for the current user scale; the item rows are quantised once per catalogue.  kpad <= 128.
+ *       for the current user scale; the item rows are quantised once per catalogue.
+ *     kpad (here and in trec_score_prep_i8_users): a multiple of 4 that is at most 64, or 128 -- what the row kernels cover;
+ *     64 < kpad < 128 is refused with TREC_ERR_INVALID and nothing is launched.  A NaN element is quantised to 0 (its row's
+ *     error norm is NaN, so every bound that uses the row is +inf); +-inf clips to +-127.
  *   User scale CLASSES (the default): one scale for all users follows the largest of them and leaves small / heavy-tailed /
  *     sparse rows a handful of levels.  trec_score_row_scale_i8: nat [n] = the scale each row wants (the best of max |x| / 127
  *     and a half / a quarter of it by the error norm each leaves), gmax [1] (zeroed) = their maximum.  The host rounds them UP to

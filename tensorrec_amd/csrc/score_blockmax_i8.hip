@@ -320,8 +320,8 @@ __global__ __launch_bounds__(256) void prep_i8_kernel(const float* __restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float q = rintf(v[e] * inv);
-            q = fminf(fmaxf(q, -127.f), 127.f);
             if (!(q == q)) q = 0.f;                                     // NaN input: the error norm below turns NaN -> the bound turns inf
+            q = fminf(fmaxf(q, -127.f), 127.f);                         // (after the NaN test: fmaxf(NaN, -127) is -127, not NaN)
             const float err = v[e] - q * scale;
             sw = fmaf(v[e], v[e], sw);
             se = fmaf(err, err, se);
@@ -415,8 +415,8 @@ __global__ __launch_bounds__(256) void bias_i8_kernel(const float* __restrict__ 
         // conversion of the maximum exact; with a scale per user class the product a_c b_s of a small user and a superblock
         // of small items is ~1e-8 and a bias of 1 is 1e8 units: clamped, the bias error made every bound useless -- fitted
         // models fell back to bf16.  The conversion now rounds (2^-24 relative): one more unit of c_K in i8_pair_err.)
+        if (!(bq == bq)) bq = 0.f;                                      // (before the clamp: fmaxf(NaN, x) is x)
         bq = fminf(fmaxf(bq, -1073741824.f), 1073741824.f);
-        if (!(bq == bq)) bq = 0.f;
         bq_c[i] = (int)bq;
         float a2 = fabsf(b), a3 = fabsf(b - bq * sp);
         if (a2 != a2) a2 = INFINITY;
@@ -569,7 +569,9 @@ extern "C" int trec_score_prep_i8(const float* repr, int64_t n, int32_t d, int32
     hipStream_t st = (hipStream_t)stream;
     if (side != 2) {
         TREC_REQUIRE(repr && out_q && row_stats, "trec_score_prep_i8: null pointer");
-        TREC_REQUIRE(d >= 1 && kpad >= d && kpad % 4 == 0 && kpad <= 128, "trec_score_prep_i8: need d <= kpad <= 128, kpad % 4 == 0");
+        // prep_i8_kernel<G> covers 8 G columns and is dispatched for G = 32 (kpad 128), 16 (kpad 64) and 8: nothing covers 64 < kpad < 128
+        TREC_REQUIRE(d >= 1 && kpad >= d && kpad % 4 == 0 && (kpad <= 64 || kpad == 128),
+                     "trec_score_prep_i8: need d <= kpad, kpad % 4 == 0, kpad <= 64 or kpad == 128");
         TREC_REQUIRE(((uintptr_t)repr % 16) == 0, "trec_score_prep_i8: repr must be 16-byte aligned");
         if (side == 0) {
             TREC_REQUIRE(workspace, "trec_score_prep_i8: the user side needs the 16-byte workspace");
@@ -586,7 +588,7 @@ extern "C" int trec_score_prep_i8(const float* repr, int64_t n, int32_t d, int32
         } else {
             hipLaunchKernelGGL(sb_scale_kernel, dim3((unsigned)ceil_div64(n, sb_rows)), dim3(1024), 0, st, repr, n, d, sb_rows, sb_stats);
         }
-        const int g = kpad >= 128 ? 32 : kpad / 4;
+        const int g = kpad == 128 ? 32 : (kpad == 64 ? 16 : 8);      // the lanes per row of the form launched below size the grid
         const unsigned blocks = (unsigned)ceil_div64(n * g, 256);
 #define TREC_PQ(GV) hipLaunchKernelGGL(prep_i8_kernel<GV>, dim3(blocks), dim3(256), 0, st, repr, n, d, kpad, scales, side == 1 ? sb_rows : 0, sb_stats, (signed char*)out_q, (float2*)row_stats, 0)
         if (g == 32) TREC_PQ(32);
@@ -629,11 +631,12 @@ extern "C" int trec_score_prep_i8_users(const float* repr, int64_t n, int32_t d,
                                         int32_t wg_rows, void* out_q, float* row_stats, void* stream)
 {
     TREC_REQUIRE(repr && wg_scale && out_q && row_stats && wg_rows >= 1, "trec_score_prep_i8_users: bad arguments");
-    TREC_REQUIRE(d >= 1 && kpad >= d && kpad % 4 == 0 && kpad <= 128, "trec_score_prep_i8_users: need d <= kpad <= 128, kpad % 4 == 0");
+    TREC_REQUIRE(d >= 1 && kpad >= d && kpad % 4 == 0 && (kpad <= 64 || kpad == 128),
+                 "trec_score_prep_i8_users: need d <= kpad, kpad % 4 == 0, kpad <= 64 or kpad == 128");
     TREC_REQUIRE(((uintptr_t)repr % 16) == 0, "trec_score_prep_i8_users: repr must be 16-byte aligned");
     if (n == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int g = kpad >= 128 ? 32 : kpad / 4;
+    const int g = kpad == 128 ? 32 : (kpad == 64 ? 16 : 8);      // the lanes per row of the form launched below size the grid
     const unsigned blocks = (unsigned)ceil_div64(n * g, 256);
 #define TREC_PQU(GV) hipLaunchKernelGGL(prep_i8_kernel<GV>, dim3(blocks), dim3(256), 0, st, repr, n, d, kpad, wg_scale, 0, (float*)nullptr, (signed char*)out_q, (float2*)row_stats, wg_rows)
     if (g == 32) TREC_PQU(32);

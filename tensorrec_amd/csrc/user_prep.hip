@@ -295,8 +295,8 @@ __global__ __launch_bounds__(256) void prep_sorted_kernel(const float* __restric
         sw = fmaf(w[e], w[e], sw);
         se = fmaf(err, err, se);
         float q = rintf(w[e] * inv);
-        q = fminf(fmaxf(q, -127.f), 127.f);
         if (!(q == q)) q = 0.f;                                           // NaN input: the error norm turns NaN -> the bound turns inf
+        q = fminf(fmaxf(q, -127.f), 127.f);                               // (after the NaN test: fmaxf(NaN, -127) is -127, not NaN)
         const float err8 = w[e] - q * a;
         se8 = fmaf(err8, err8, se8);
         pq |= ((unsigned int)(int)q & 0xffu) << (8 * e);
