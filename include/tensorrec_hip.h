@@ -870,6 +870,25 @@ int trec_sample_items(int64_t n_users, int64_t user_base, int32_t n_items, int32
  * TREC_ERR_INVALID for a null pointer, n_items < 1, n_sampled < 1; n_users == 0 is a no-op.                              */
 int trec_sample_items_alias(int64_t n_users, int64_t user_base, int32_t n_items, int32_t n_sampled, const uint32_t* thr,
                             const int32_t* alias, uint64_t seed, uint32_t step, int32_t* out, void* stream);
+/* Dynamic negative sampling (csrc/sampler_hard.hip, docs/hard_negatives.md; no counterpart in the reference): from the candidate
+ * table `candidates` int32 [n_users, n_candidates] the kernel returns out int32 [n_users, n_sampled].  Candidate j of user u scores
+ * y_j = U[u] . V[c_j] (+ item_bias[c_j]) in float32, one fixed summation order (stated in the file), no float atomics; it is a HIT
+ * when `exclude` is set and c_j is the column of an interaction of u with pos_slot >= 0 (indptr / x_item / pos_slot: the CSR rows
+ * of sparse.Interactions).  ORDER: non-hits before hits; non-hits by descending score (NaN counts as -inf), equal scores by
+ * ascending position j; hits by ascending j.  Slots [0, n_hard) hold the first n_hard candidates of that order; slots
+ * [n_hard, n_sampled) the first n_sampled - n_hard of the REMAINING candidates in the order "non-hits before hits, ascending j".
+ * out_scores (nullable) float [n_users, n_candidates]: every y_j as computed.  U [n_users, d], V [n_items, d].
+ * Coverage: 1 <= n_hard <= n_sampled <= n_candidates <= 4096, d a multiple of 4 in [4, 256] -- trec_hard_negatives_supported
+ * (host arithmetic, no stream argument) is the one statement of it and returns 1 / 0.
+ * TREC_ERR_INVALID before any launch for a null U / V / candidates / out, null interaction arrays with `exclude`, n_users
+ * outside [0, 2^31), n_items outside [1, 2^31), n_candidates < 1, n_sampled outside [1, n_candidates], n_hard outside
+ * [1, n_sampled], d < 1; TREC_ERR_UNSUPPORTED where _supported says 0; n_users == 0 is a no-op.  A candidate id outside
+ * [0, n_items) is the caller's error (no out-of-range read, undefined result).                                              */
+int trec_hard_negatives_supported(int32_t n_candidates, int32_t n_sampled, int32_t d);
+int trec_select_hard_negatives(const float* U, const float* V, const float* item_bias, const int64_t* indptr,
+                               const int32_t* x_item, const int32_t* pos_slot, const int32_t* candidates, int64_t n_users,
+                               int64_t n_items, int32_t n_candidates, int32_t n_sampled, int32_t n_hard, int32_t d,
+                               int32_t exclude, int32_t* out, float* out_scores, void* stream);
 
 /* ---- K8: optimiser --------------------------------------------------------------------------------------------
  * tf.train.AdamOptimizer(lr).minimize (tensorrec.py:489) + gradient of alpha * sum(tf.nn.l2_loss(w)) (:487-488):

@@ -4,7 +4,7 @@ RepresentationGraph / PredictionGraph / LossGraph classes (module layout of tens
 
 Importing the package does not need a GPU; running any model does (there is no CPU execution path).
 """
-from .tensorrec import TensorRec, DeviceSampler, HostSampler, ReplaySampler, PopularitySampler
+from .tensorrec import TensorRec, DeviceSampler, HostSampler, ReplaySampler, PopularitySampler, HardNegativeSampler
 from . import errors
 from . import eval  # noqa: A004
 from . import framework
@@ -18,6 +18,6 @@ from . import util
 __version__ = '0.1.0'
 
 __all__ = [
-    "TensorRec", "DeviceSampler", "HostSampler", "ReplaySampler", "PopularitySampler", "errors", "eval", "framework", "input_utils", "loss_graphs",
+    "TensorRec", "DeviceSampler", "HostSampler", "ReplaySampler", "PopularitySampler", "HardNegativeSampler", "errors", "eval", "framework", "input_utils", "loss_graphs",
     "prediction_graphs", "recommendation_graphs", "representation_graphs", "util",
 ]

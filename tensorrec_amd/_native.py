@@ -182,6 +182,8 @@ SIGNATURES = {
     "trec_rmse_bwd": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_sample_items": [_i64, _i64, _i32, _i32, _i32, _u64, _u32, _vp, _vp],
     "trec_sample_items_alias": [_i64, _i64, _i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp],
+    "trec_hard_negatives_supported": [_i32, _i32, _i32],
+    "trec_select_hard_negatives": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "trec_crc32c": [_vp, _u64, _u32],
     "trec_collapse_tastes_fwd": [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_collapse_tastes_bwd": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],

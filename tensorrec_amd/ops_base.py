@@ -1773,6 +1773,37 @@ def sample_items_alias(n_users, n_items, n_sampled, thr, alias, seed, step, devi
     return out
 
 
+def hard_negatives_supported(n_candidates, n_sampled, d):
+    """Does csrc/sampler_hard.hip cover this shape?  The native library's own statement (host arithmetic, needs no GPU)."""
+    return bool(N.query("trec_hard_negatives_supported", int(n_candidates), int(n_sampled), int(d)))
+
+
+def select_hard_negatives(user_in, item_in, item_bias, interactions, candidates, n_sampled, n_hard=None, exclude=True,
+                          return_scores=False):
+    """int32 [n_users, n_sampled] chosen from the int32 [n_users, M] table ``candidates`` by the scores user_in . item_in
+    (+ item_bias): the ``n_hard`` (None: all) highest-scoring first, then the first of the rest by position; with ``exclude`` the
+    accidental hits of ``interactions`` go last (csrc/sampler_hard.hip, the definition: docs/hard_negatives.md).  ``interactions``
+    may be None without ``exclude``.  With ``return_scores`` also the float32 [n_users, M] scores.  Nothing is checked on the host
+    but the shapes, and nothing is read back: an id outside [0, n_items) is the caller's error."""
+    u, v, _, ib = _step_operands(user_in, item_in, None, item_bias)
+    if candidates.dim() != 2 or candidates.shape[0] != u.shape[0]:
+        raise ValueError("candidates must be an [n_users, n_candidates] table")
+    candidates = candidates.to(torch.int32).contiguous()
+    n_users, M, d = int(u.shape[0]), int(candidates.shape[1]), int(u.shape[1])
+    n_sampled = int(n_sampled)
+    n_hard = n_sampled if n_hard is None else int(n_hard)
+    out = torch.empty((n_users, n_sampled), dtype=torch.int32, device=u.device)
+    scores = torch.empty((n_users, M), dtype=torch.float32, device=u.device) if return_scores else None
+    if n_users == 0:                    # (an empty tensor has no address to hand over)
+        return (out, scores) if return_scores else out
+    exclude = bool(exclude) and interactions.nnz > 0          # (nor have the arrays of a batch without interactions: nothing hits)
+    rows = (interactions.indptr, interactions.x_item32, interactions.pos_slot) if exclude else (None, None, None)
+    with _timed("select_hard_negatives"):
+        N.call("trec_select_hard_negatives", N.ptr(u), N.ptr(v), N.ptr(ib), N.ptr(rows[0]), N.ptr(rows[1]), N.ptr(rows[2]),
+               N.ptr(candidates), n_users, int(v.shape[0]), M, n_sampled, n_hard, d, 1 if exclude else 0, N.ptr(out), N.ptr(scores))
+    return (out, scores) if return_scores else out
+
+
 def adam_tf_step(w, m, v, grad, lr_t, l2_coef, beta1=0.9, beta2=0.999, eps=1e-8):
     with _timed("adam_tf_step"):
         N.call("trec_adam_tf_step", N.ptr(w), N.ptr(m), N.ptr(v), N.ptr(_f32c(grad)), w.numel(), float(lr_t), beta1, beta2,

@@ -99,12 +99,15 @@ def warp_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row
 
 
 def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,
-                   n_items, n_sampled, dense_loss):
+                   n_items, n_sampled, dense_loss, scored_sampler=False):
     """May this batch's step be captured in a HIP graph and replayed?  Single process, no gradient capture, no deterministic grouping;
     shared negatives draw one row per step and stay eager (docs/sampled_losses.md); only steps made of the library's own launches are
     captured (``loss_capturable``: a built-in loss class, ``engine_graph``: a built-in prediction graph -- user-defined torch code may
     sync or allocate, capturing it would fail, warn and fall back on every fit call); ``n_graphs`` graphs are held already; and the
-    step is small enough to be bound by its launches."""
+    step is small enough to be bound by its launches.  ``scored_sampler``: the sampler reads the step's representations
+    (tensorrec.HardNegativeSampler) -- such a step stays eager (docs/hard_negatives.md)."""
+    if scored_sampler:
+        return False
     if not hip_graphs or dp or capturing or deterministic or shared_negatives or not loss_capturable or not engine_graph:
         return False
     if n_graphs >= MAX_GRAPHED_BATCHES:
@@ -114,11 +117,14 @@ def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, l
 
 
 def coop_covered(dp, capturing, deterministic, multi, attention, linear_user, linear_item, dot_product, wmrb, identity_users,
-                 n_user_rows, n_users, n_items, d, n_sampled, max_row_nnz, switches=None):
+                 n_user_rows, n_users, n_items, d, n_sampled, max_row_nnz, switches=None, scored_sampler=False):
     """The stateless part of "does the whole step run as ONE cooperative kernel" (csrc/step_coop.hip): single process, one taste, no
     attention, Linear representations on both sides (the four graph classes arrive as booleans: exact built-in classes only),
     DotProduct, WMRB / BalancedWMRB, identity user features with one row per user, n_sampled <= n_items, and a model the kernel's
-    workspace query accepts.  What the variable store and the Adam slots must look like is state: _CoopStep.plan checks it."""
+    workspace query accepts.  What the variable store and the Adam slots must look like is state: _CoopStep.plan checks it.
+    ``scored_sampler``: as in graph_eligible -- the kernel draws its own uniform samples, so such a model is not covered."""
+    if scored_sampler:
+        return False
     sw = read_switches() if switches is None else switches
     if not sw.fit_step_coop or dp or capturing or deterministic or multi or attention:
         return False

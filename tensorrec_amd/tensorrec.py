@@ -203,6 +203,60 @@ class ReplaySampler(object):
         return torch.from_numpy(table).to(device)
 
 
+class HardNegativeSampler(object):
+    """Dynamic negative sampling: ``base`` (anything with the ``sample`` protocol; None: DeviceSampler(seed)) draws ``n_candidates``
+    items per user, the candidates are scored with the step's CURRENT representations on the device, and the step trains on the
+    ``n_hard`` (None: all n_sampled_items) highest-scoring ones followed by the first n_sampled_items - n_hard of the others in the
+    order drawn (csrc/sampler_hard.hip; the definition, the WARP caveat and what is not covered: docs/hard_negatives.md).  With
+    ``exclude_positives`` a candidate that is one of the user's positives is taken only when nothing else is left, and then last.
+
+    ``scored = True``: the fit hands such a sampler the step's operands through ``sample_scored`` instead of calling ``sample``.  Step,
+    ``replace``, device and ``user_base`` go to ``base`` unchanged, so user shards and batches draw the candidates the whole
+    population would.  There is no ``log_q``: the selection changes the distribution, so no logQ correction applies.
+    ``keep_last=True`` keeps the last returned table and its candidates on the device (``last_table``, ``last_candidates``)."""
+    scored = True
+
+    def __init__(self, n_candidates, base=None, n_hard=None, exclude_positives=True, seed=0, keep_last=False):
+        if isinstance(n_candidates, bool) or not isinstance(n_candidates, (int, np.integer)) or n_candidates < 1:
+            raise ValueError("n_candidates must be an int >= 1, got %r" % (n_candidates,))
+        if n_hard is not None and (isinstance(n_hard, bool) or not isinstance(n_hard, (int, np.integer)) or n_hard < 1):
+            raise ValueError("n_hard must be None or an int >= 1, got %r" % (n_hard,))
+        if getattr(base, 'scored', False):
+            raise ValueError("base must draw without the model: a scored sampler cannot be the base of another")
+        self.n_candidates = int(n_candidates)
+        self.n_hard = None if n_hard is None else int(n_hard)
+        self.exclude_positives = bool(exclude_positives)
+        self.seed = int(seed)
+        self.base = base if base is not None else DeviceSampler(self.seed)
+        self.keep_last = bool(keep_last)
+        self.last_table = self.last_candidates = None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["last_table"] = state["last_candidates"] = None          # device tensors stay behind (save_model pickles the model object)
+        return state
+
+    def sample(self, n_items, n_users, n_sampled_items, replace, step, device, user_base=0):
+        raise TypeError("HardNegativeSampler chooses by the model's scores: call sample_scored(user_in, item_in, item_bias, "
+                        "interactions, n_sampled_items, replace, step, device, user_base)")
+
+    def sample_scored(self, user_in, item_in, item_bias, interactions, n_sampled_items, replace, step, device, user_base=0):
+        """int32 [n_users, n_sampled_items]: drawn by ``base`` as [n_users, n_candidates], chosen by user_in . item_in (+ item_bias)"""
+        n_users, n_items = interactions.shape
+        S = int(n_sampled_items)
+        if self.n_candidates < S:
+            raise ValueError("n_candidates = %d is below n_sampled_items = %d" % (self.n_candidates, S))
+        if self.n_hard is not None and self.n_hard > S:
+            raise ValueError("n_hard = %d is above n_sampled_items = %d" % (self.n_hard, S))
+        candidates = self.base.sample(n_items, n_users, self.n_candidates, replace, step, device, user_base)
+        candidates = candidates.to(torch.int32).contiguous()
+        table = ops.select_hard_negatives(user_in, item_in, item_bias, interactions, candidates, S, self.n_hard,
+                                          exclude=self.exclude_positives)
+        if self.keep_last:
+            self.last_table, self.last_candidates = table, candidates
+        return table
+
+
 def _beta_powers(t, start=None):
     """(beta1^t, beta2^t) as the float32 running products TF keeps [external]; ``start``: (t0, beta1^t0, beta2^t0) to go on from."""
     t0, b1p, b2p = start or (0, np.float32(1.0), np.float32(1.0))
@@ -307,7 +361,8 @@ class TensorRec(object):
         at 1M x 1M.  Default False: reproducible up to fp32 summation order, like TF's own GPU kernels.
         :param device: torch device; default 'cuda' (there is no CPU execution path).
         :param sampler: object with ``sample(n_items, n_users, n_sampled_items, replace, step, device)``;
-        default DeviceSampler(seed).
+        default DeviceSampler(seed).  A sampler with ``scored = True`` (HardNegativeSampler) is handed the step's
+        representations through ``sample_scored`` instead (docs/hard_negatives.md).
         :param seed: int or None -- seeds weight initialisation and the default sampler.
         :param data_parallel: if True and torch.distributed is initialised, ``fit`` is data-parallel over USERS: every
         rank passes its own rows of ``interactions`` / ``user_features`` (and ``user_offset=`` its first global user
@@ -760,18 +815,55 @@ class TensorRec(object):
         return step_plan.graph_eligible(
             self.hip_graphs, self._dp_active(), self._capture is not None, getattr(self, 'deterministic', False),
             self._shared_negatives(), type(self.loss_graph_factory) in _GRAPH_CAPTURABLE_LOSSES, self._is_engine_graph(),
-            len(self._graph_pool_owner), inter.nnz, inter.shape[0], inter.shape[1], n_sampled_items, self.loss_graph_factory.is_dense)
+            len(self._graph_pool_owner), inter.nnz, inter.shape[0], inter.shape[1], n_sampled_items, self.loss_graph_factory.is_dense,
+            scored_sampler=self._scored_sampler())
 
     def _shared_negatives(self):
         """The loss graph asks for ONE row of samples per step, shared by every user (SampledSoftmaxLossGraph(shared_negatives=True))."""
         loss_graph = self.loss_graph_factory
         return bool(loss_graph.is_sample_based and getattr(loss_graph, 'shared_negatives', False))
 
-    def _draw_samples(self, inter, n_sampled_items):
+    def _scored_sampler(self):
+        """The sampler chooses by the model's scores (HardNegativeSampler): it is handed the step's operands, and the step is eager."""
+        return bool(getattr(self.sampler, 'scored', False))
+
+    def _check_scored_sampler(self, u_in, i_in, n_sampled_items):
+        """What a scored sampler needs of the model and the step (docs/hard_negatives.md): ValueError naming the condition that fails"""
+        graph, loss_graph = self.prediction_graph_factory, self.loss_graph_factory
+
+        def refuse(what):
+            raise ValueError("a scored sampler (%s) %s" % (type(self.sampler).__name__, what))
+        if not self._is_engine_graph() or getattr(graph, 'engine_mode', None) != ops.MODE_DOT:
+            refuse("needs a built-in dot-product or cosine prediction graph: Euclidean and user-defined scores are not covered")
+        if self._multi():
+            refuse("needs one taste and no attention graph")
+        if u_in is None or i_in is None or u_in.dim() != 2 or i_in.dim() != 2 or u_in.shape[1] != i_in.shape[1]:
+            refuse("needs two-dimensional, equally wide user and item representations")
+        if self._shared_negatives():
+            refuse("does not go with shared negatives: it chooses per user")
+        if getattr(loss_graph, 'log_q_correction', False):
+            refuse("does not go with log_q_correction: the selection changes the distribution the correction assumes")
+        if self._dp_active():
+            refuse("is not covered by a data-parallel fit")
+        n_candidates = int(getattr(self.sampler, 'n_candidates', n_sampled_items))
+        if n_candidates >= int(n_sampled_items) and \
+                not ops.hard_negatives_supported(n_candidates, int(n_sampled_items), int(u_in.shape[1])):
+            refuse("does not cover n_candidates = %d, n_sampled_items = %d, n_components = %d (ops.hard_negatives_supported)"
+                   % (n_candidates, int(n_sampled_items), int(u_in.shape[1])))
+
+    def _draw_samples(self, inter, n_sampled_items, u_in=None, i_in=None, item_bias=None):
         """tf.py_func(sample_items) of tensorrec.py:298-302: one [n_users, n_sampled_items] int32 table per step -- or, with shared
         negatives, ONE [1, n_sampled_items] row: the stream of user 0 on every batch and every rank, so a data-parallel fit draws
-        the set a single process would."""
+        the set a single process would.  A scored sampler gets the step's operands (``u_in``, ``i_in``: normalised for cosine, so it
+        ranks by cosine; ``item_bias``: None for an unbiased model) and chooses outside autograd."""
         n_users, n_items = inter.shape
+        if self._scored_sampler():               # (_train_step has checked the model: _check_scored_sampler)
+            self._sample_step += 1
+            with torch.no_grad():
+                samples = self.sampler.sample_scored(u_in, i_in, item_bias, inter, int(n_sampled_items),
+                                                     self.loss_graph_factory.is_sampled_with_replacement, self._sample_step,
+                                                     self._store.device, getattr(inter, 'user_base', 0))
+            return samples.to(torch.int32).contiguous()
         self._sample_step += 1
         shared = self._shared_negatives()
         samples = self.sampler.sample(n_items, 1 if shared else n_users, int(n_sampled_items),
@@ -798,6 +890,8 @@ class TensorRec(object):
             # a one-pass step kernel instead of serial scores -> loss -> autograd, where step_plan.kernel names one
             shared = self._shared_negatives()
             same_width = item_repr.dim() == 2 and user_repr.dim() == 2 and user_repr.shape[1] == item_repr.shape[1]
+            if loss_graph.is_sample_based and self._scored_sampler():
+                self._check_scored_sampler(None if multi else user_repr, item_repr, n_sampled_items)
             kernel = step_plan.kernel(step_plan.loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi, same_width,
                                       n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]), shared,
                                       getattr(loss_graph, 'remove_accidental_hits', False))
@@ -859,7 +953,8 @@ class TensorRec(object):
                                     'tf_rankings': None if builtin else rank_predictions(tf_prediction)})
             if loss_graph.is_sample_based:
                 if samples is None:
-                    samples = self._draw_samples(inter, n_sampled_items)
+                    samples = self._draw_samples(inter, n_sampled_items, None if multi else u_in, i_in,
+                                                 item_bias if self.biased else None)
                 if shared and samples.shape[0] == 1 and n_users != 1:
                     samples = samples.expand(n_users, samples.shape[1]).contiguous()     # the definition: every row is the shared one
                 if engine:
@@ -908,7 +1003,7 @@ class TensorRec(object):
         sampler when it has one; autograd then only carries them through the representation graphs (K1 backward)."""
         loss_graph = self.loss_graph_factory
         if samples is None:
-            samples = self._draw_samples(inter, n_sampled_items)
+            samples = self._draw_samples(inter, n_sampled_items, u_in, i_in, item_bias if self.biased else None)
         self.last_step_kernel = kernel
         operands = (u_in, i_in, user_bias if self.biased else None, item_bias if self.biased else None, inter)
         if kernel == "wmrb_fused":
@@ -2046,7 +2141,7 @@ class _CoopStep(object):
                 type(model.item_repr_graph_factory) is LinearRepresentationGraph,
                 type(model.prediction_graph_factory) is DotProductPredictionGraph,
                 step_plan.loss_kind(model.loss_graph_factory) in step_plan.WMRB_KINDS, getattr(uf, "is_identity", False), uf.shape[0],
-                n_users, n_items, d, n_sampled_items, inter.max_row_nnz):
+                n_users, n_items, d, n_sampled_items, inter.max_row_nnz, scored_sampler=model._scored_sampler()):
             return None
         store = model._store
         names = ["linear_weights_user_0", "linear_weights_item"] + (["user_feature_biases", "item_feature_biases"] if model.biased else [])
