@@ -780,6 +780,29 @@ int trec_wmrb_tiled_step(const float* U, const float* V, const float* user_bias,
                          int32_t max_interactions_per_user, float* loss, float* pred_serial, float* dU, float* d_user_bias,
                          float* val_samples, float* val_pairs, float* raw_samples, float* raw_pairs, float* dense_g,
                          int64_t ldg, float* val_rowsum, void* stream);
+/* The tiled step with the SAMPLED SOFTMAX loss (csrc/softmax_tiled.hip; the loss is this project's own, docs/sampled_losses.md --
+ * the scores are those of the reference's serial prediction graphs, prediction_graphs.py:52-55 dot, :105-117 euclidean): the
+ * frame, the modes and every output of trec_wmrb_tiled_step -- the two sweeps are the same code (csrc/tiled_pass_parts.hpp) --
+ * without pos_weight and with the loss arguments of trec_softmax_fused_step: inv_temperature (finite, > 0), log_q_correction
+ * (log q from log_q [n_items] or, with log_q NULL, log_uniform = -log(n_items); n_items in [1, 2^31)), remove_hits (a sample
+ * whose item is the column of one of the user's interactions with pos_slot >= 0 leaves the sums and gets a value of exactly 0:
+ * one binary search through the user's row per sample; a user whose samples are all hits gets loss 0 and zero values).  The
+ * loss is trec_sampled_softmax_fwd / _bwd's, or trec_sampled_softmax_adj_fwd / _bwd's when a flag is set, at upstream gradient
+ * 1, with fixed summation orders: apart from the float atomics into dense_g every output is the same bits in every call.
+ * trec_softmax_tiled_lds_bytes: dynamic LDS of the launch, or -1 when not covered (d % 4 == 0, 4 <= d <= 512, n_sampled >= 1, and
+ * 2 (n_sampled + longest row) + n_sampled + 8 d (16 d for d <= 64) + 24 floats within 128 KB).  Errors before any launch:
+ * TREC_ERR_INVALID for null pointers, a mode other than 0 / 1, a bad inv_temperature, user_bias without d_user_bias or the
+ * reverse, raw_samples without raw_pairs or the reverse, dU NULL without dense_g and val_rowsum, ldg < n_items, n_items out of
+ * range with the correction, null interaction arrays with remove_hits; TREC_ERR_UNSUPPORTED for a shape the query answers
+ * with -1 (then run the generic step).  n_users == 0: TREC_OK, no launch. */
+int trec_softmax_tiled_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d);
+int trec_softmax_tiled_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
+                            const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const int32_t* samples,
+                            int64_t n_users, int64_t n_items, int32_t n_sampled, int32_t d, int32_t mode,
+                            int32_t max_interactions_per_user, float inv_temperature, const float* log_q, float log_uniform,
+                            int32_t log_q_correction, int32_t remove_hits, float* loss, float* pred_serial, float* dU,
+                            float* d_user_bias, float* val_samples, float* val_pairs, float* raw_samples, float* raw_pairs,
+                            float* dense_g, int64_t ldg, float* val_rowsum, void* stream);
 /* ONE kernel per training step for models that fit on chip (csrc/step_coop.hip; BASELINE.json configs[1]): the whole of
  * session.run(tf_optimizer) (tensorrec.py:617-622) for LinearRepresentation (identity user features; any item features) + DotProduct +
  * WMRB / BalancedWMRB -- item tower forward, sampling, the tiled WMRB step per user, d V = G^T . U, item tower backward, TF-form Adam on

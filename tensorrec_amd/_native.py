@@ -166,6 +166,9 @@ SIGNATURES = {
     "trec_wmrb_tiled_lds_bytes": [_i32, _i32, _i32],
     "trec_wmrb_tiled_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "trec_softmax_tiled_lds_bytes": [_i32, _i32, _i32],
+    "trec_softmax_tiled_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f, _vp, _f, _i32, _i32,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "trec_fit_step_coop_workspace_floats": [_i64, _i64, _i32, _i32, _i32],
     "trec_fit_step_coop": [_vp] * 12 + [_vp] * 6 + [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32, _i32, _i64, _u64, _u32, _f, _f, _f, _f, _f,
                                                             _vp, _i64, _vp, _vp, _vp],

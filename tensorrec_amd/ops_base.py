@@ -898,13 +898,14 @@ GROUP_BINNED_MIN_PAIRS = int(_os.environ.get("TREC_BINNED_MIN_PAIRS", 1 << 22)) 
 
 def step_switch(name):
     """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT,
-    "softmax_full" to SOFTMAX_FULL_DEFAULT, "warp_fused" to WARP_FUSED_DEFAULT.)"""
-    default = {"softmax_shared": SOFTMAX_SHARED_DEFAULT, "softmax_full": SOFTMAX_FULL_DEFAULT, "warp_fused": WARP_FUSED_DEFAULT}.get(name, 1)
+    "softmax_full" to SOFTMAX_FULL_DEFAULT, "warp_fused" to WARP_FUSED_DEFAULT, "softmax_tiled" to SOFTMAX_TILED_DEFAULT.)"""
+    default = {"softmax_shared": SOFTMAX_SHARED_DEFAULT, "softmax_full": SOFTMAX_FULL_DEFAULT, "warp_fused": WARP_FUSED_DEFAULT,
+               "softmax_tiled": SOFTMAX_TILED_DEFAULT}.get(name, 1)
     return N.load().trec_get_tuning(name.encode(), default) != 0
 
 
 def step_covers(kernel, n_sampled, max_row_nnz, d):
-    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "warp_fused", "softmax_shared") cover this shape?  The ONE
+    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_tiled", "warp_fused", "softmax_shared") cover this shape?  The ONE
     statement of the coverage: the native library's shape query (host arithmetic, needs no GPU); step_plan.kernel and the
     ``*_supported`` functions below both ask here."""
     if kernel == "softmax_shared":         # (the interactions do not restrict it: the positives are O(P) work on K3's scores)
@@ -1261,42 +1262,50 @@ def _dense_g_fits(n_users, n_items, n_sampled, nnz, dev):
     return need <= 0.4 * free
 
 
-def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, samples, balanced=False, mode=MODE_DOT):
-    """wmrb_fused_step for S in the thousands, long rows and Euclidean scores: (loss [P+], pred_serial [P], d user_in, d item_in,
-    d user_bias, d item_bias), upstream gradient 1.  User side: ONE kernel, the user's item rows streamed twice (scores into LDS,
-    then dU).  Item side: when a user's pairs are a sizeable share of the catalogue (configs[4]: 10 %), the pairs' values were
-    also added into a dense G [n_users, n_items] and d item_in is G^T . U on fp32 MFMA -- no sort, no second gather of 3.7e8
-    rows; otherwise the grouped gathers of the composed path (transposed interactions + counting sort of the samples)."""
+def _tiled_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples, mode):
+    """What the tiled one-pass steps (wmrb_tiled_step, softmax_tiled_step) start from: (u, v, ub, ib) of _step_operands, the int32
+    sample table, and a dict of what both allocate -- loss [P+], pred [P], d_u (None on the dense-G route: dU comes from G . V),
+    d_ub or None, val_s [U, S], val_p [P], raw_s / raw_p (Euclidean with item biases, else None), G [n_users, ldg] zeroed or None,
+    ldg, val_rs [U] or None -- plus xs (the table flattened), euclid and dense (is the item side the dense-G GEMMs)."""
     u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
     n_users, n_items = interactions.shape
-    S, d, dev, nnz = int(samples.shape[1]), u.shape[1], u.device, interactions.nnz
+    S, dev, nnz = int(samples.shape[1]), u.device, interactions.nnz
     euclid = mode == MODE_EUCLIDEAN
-    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
-    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
-    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
-    val_s = torch.empty((n_users, S), dtype=torch.float32, device=dev)
-    val_p = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    t = dict(euclid=euclid)
+    t["loss"] = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    t["pred"] = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    t["d_ub"] = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    t["val_s"] = torch.empty((n_users, S), dtype=torch.float32, device=dev)
+    t["val_p"] = torch.empty((nnz,), dtype=torch.float32, device=dev)
     need_raw = euclid and ib is not None
-    raw_s = torch.empty((n_users, S), dtype=torch.float32, device=dev) if need_raw else None
-    raw_p = torch.empty((nnz,), dtype=torch.float32, device=dev) if need_raw else None
-    weight = interactions.balanced_weight() if balanced else None
+    t["raw_s"] = torch.empty((n_users, S), dtype=torch.float32, device=dev) if need_raw else None
+    t["raw_p"] = torch.empty((nnz,), dtype=torch.float32, device=dev) if need_raw else None
     samples = samples.to(torch.int32).contiguous()
-    xs = samples.reshape(-1)
+    t["xs"] = samples.reshape(-1)
     dense = _dense_g_fits(n_users, n_items, S, nnz, dev) and not _LOCAL.deterministic_grouping
-    ldg = (n_items + 3) // 4 * 4
-    G = torch.zeros((n_users, ldg), dtype=torch.float32, device=dev) if dense else None
+    t["dense"] = dense
+    t["ldg"] = (n_items + 3) // 4 * 4
+    t["G"] = torch.zeros((n_users, t["ldg"]), dtype=torch.float32, device=dev) if dense else None
     # with G the user side needs no second sweep over the rows either: dU = G . V (euclidean: rowsum(G) U - G . V)
-    d_u = None if dense else torch.empty_like(u)
-    val_rs = torch.empty((n_users,), dtype=torch.float32, device=dev) if dense else None
-    with _timed("wmrb_tiled_step"):
-        N.call("trec_wmrb_tiled_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
-               N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(weight), N.ptr(samples), n_users, n_items, S, d,
-               int(mode), int(interactions.max_row_nnz), N.ptr(loss), N.ptr(pred), N.ptr(d_u), N.ptr(d_ub), N.ptr(val_s),
-               N.ptr(val_p), N.ptr(raw_s), N.ptr(raw_p), N.ptr(G), ldg, N.ptr(val_rs))
+    t["d_u"] = None if dense else torch.empty_like(u)
+    t["val_rs"] = torch.empty((n_users,), dtype=torch.float32, device=dev) if dense else None
+    return u, v, ub, ib, samples, t
+
+
+def _tiled_item_side(u, v, ib, interactions, S, t):
+    """The item side of a tiled one-pass step (wmrb_tiled_step, softmax_tiled_step) from the values its kernel left in ``t``
+    (_tiled_step_buffers): the dense-G GEMMs when G was filled, otherwise the grouped gathers; trec_item_weighted_hist for Euclidean
+    scores with item biases.  Returns (d_u, d_v, d_ib)."""
+    n_users, n_items = interactions.shape
+    d, dev, nnz = u.shape[1], u.device, interactions.nnz
+    euclid, dense, ldg, xs = t["euclid"], t["dense"], t["ldg"], t["xs"]
+    val_s, val_p, raw_s, raw_p, val_rs, d_u = t["val_s"], t["val_p"], t["raw_s"], t["raw_p"], t["val_rs"], t["d_u"]
+    need_raw = raw_s is not None
     LAST_FUSED_STATS["route"] = "tiled+dense_g" if dense else "tiled+grouped"
     LAST_FUSED_STATS["drop_zero"] = False
     d_ib = None
     if dense:
+        G = t.pop("G")
         # d item_in: dot  dV[i] = sum_u G[u, i] U[u];  euclidean  dV[i] = sum c (V[i] - U[u]) = colsum(G)[i] V[i] - (G^T U)[i]
         # (both GEMMs are gradients, held to 1e-4: split-bf16 operands on bf16 MFMA, bound by reading G instead of by the fp32
         # matrix pipe -- tuning dense_g_split_bf16 = 0: exact fp32 products)
@@ -1314,12 +1323,12 @@ def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, sample
         d_u = val_rs.unsqueeze(1) * uc - gv if euclid else gv
         want_cs = euclid or ib is not None
         with _timed("dense_g_gemm"):                          # (the column sums of G ride in the threads that stage it)
-            t = gemm_raw(G, uc, trans_a=True, split_bf16=split, a_colsum=want_cs and split)
-            t, cs = t if (want_cs and split) else (t, None)
-            t = t[:n_items]
+            tg = gemm_raw(G, uc, trans_a=True, split_bf16=split, a_colsum=want_cs and split)
+            tg, cs = tg if (want_cs and split) else (tg, None)
+            tg = tg[:n_items]
         if want_cs:
             cs = cs[:n_items] if cs is not None else colsum(G)[:n_items]
-        d_v = cs.unsqueeze(1) * vc - t if euclid else t.contiguous()
+        d_v = cs.unsqueeze(1) * vc - tg if euclid else tg.contiguous()
         if ib is not None and not euclid:
             d_ib = cs.contiguous()
         del G
@@ -1340,7 +1349,63 @@ def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, sample
         with _timed("item_weighted_hist"):
             N.call("trec_item_weighted_hist", N.ptr(xs), N.ptr(raw_s.reshape(-1)), int(xs.numel()), N.ptr(interactions.x_item32),
                    N.ptr(raw_p), int(nnz), int(n_items), N.ptr(d_ib))
-    return loss, pred, d_u, d_v, d_ub, d_ib
+    return d_u, d_v, d_ib
+
+
+def wmrb_tiled_step(user_in, item_in, user_bias, item_bias, interactions, samples, balanced=False, mode=MODE_DOT):
+    """wmrb_fused_step for S in the thousands, long rows and Euclidean scores: (loss [P+], pred_serial [P], d user_in, d item_in,
+    d user_bias, d item_bias), upstream gradient 1.  User side: ONE kernel, the user's item rows streamed twice (scores into LDS,
+    then dU).  Item side (_tiled_item_side): when a user's pairs are a sizeable share of the catalogue (configs[4]: 10 %), the
+    pairs' values were also added into a dense G [n_users, n_items] and d item_in is G^T . U on fp32 MFMA -- no sort, no second
+    gather of 3.7e8 rows; otherwise the grouped gathers of the composed path (transposed interactions + counting sort of the
+    samples)."""
+    u, v, ub, ib, samples, t = _tiled_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples, mode)
+    n_users, n_items = interactions.shape
+    S, d = int(samples.shape[1]), u.shape[1]
+    weight = interactions.balanced_weight() if balanced else None
+    with _timed("wmrb_tiled_step"):
+        N.call("trec_wmrb_tiled_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
+               N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(weight), N.ptr(samples), n_users, n_items, S, d,
+               int(mode), int(interactions.max_row_nnz), N.ptr(t["loss"]), N.ptr(t["pred"]), N.ptr(t["d_u"]), N.ptr(t["d_ub"]),
+               N.ptr(t["val_s"]), N.ptr(t["val_p"]), N.ptr(t["raw_s"]), N.ptr(t["raw_p"]), N.ptr(t["G"]), t["ldg"],
+               N.ptr(t["val_rs"]))
+    d_u, d_v, d_ib = _tiled_item_side(u, v, ib, interactions, S, t)
+    return t["loss"], t["pred"], d_u, d_v, t["d_ub"], d_ib
+
+
+SOFTMAX_TILED_DEFAULT = 0        # tuning "softmax_tiled" when nobody set it: the route is opt-in (docs/sampled_losses.md, "The tiled one-pass step (sampled softmax)")
+
+
+def softmax_tiled_supported(n_sampled, interactions, d):
+    """Can the tiled one-pass sampled-softmax step (csrc/softmax_tiled.hip: any S, long rows, dot or Euclidean scores) run this
+    shape, and is tuning ``softmax_tiled`` on (it defaults to off)?"""
+    return _step_supported("softmax_tiled", n_sampled, interactions, d)
+
+
+def softmax_tiled_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
+                       log_q_correction=False, remove_accidental_hits=False, mode=MODE_DOT):
+    """softmax_fused_step for S in the thousands, long rows and Euclidean scores (``mode``): the frame and the item side of
+    wmrb_tiled_step around the loss of sampled_softmax_loss (``temperature``, ``sample_log_q``, ``log_q_correction``,
+    ``remove_accidental_hits`` as there).  Returns (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias),
+    upstream gradient 1."""
+    temperature = _checked_temperature(temperature)
+    if samples.dim() != 2 or samples.shape[0] != interactions.shape[0]:
+        raise ValueError("samples must be an [n_users, n_sampled] table")
+    if mode not in (MODE_DOT, MODE_EUCLIDEAN):
+        raise ValueError("mode must be MODE_DOT or MODE_EUCLIDEAN, got %r" % (mode,))
+    u, v, ub, ib, samples, t = _tiled_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples, mode)
+    n_users, n_items = interactions.shape
+    S, d = int(samples.shape[1]), u.shape[1]
+    log_q = _checked_log_q(sample_log_q, n_items) if log_q_correction and sample_log_q is not None else None
+    with _timed("softmax_tiled_step"):
+        N.call("trec_softmax_tiled_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
+               N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(samples), n_users, n_items, S, d, int(mode),
+               int(interactions.max_row_nnz), 1.0 / temperature, N.ptr(log_q), -math.log(n_items), 1 if log_q_correction else 0,
+               1 if remove_accidental_hits else 0, N.ptr(t["loss"]), N.ptr(t["pred"]), N.ptr(t["d_u"]), N.ptr(t["d_ub"]),
+               N.ptr(t["val_s"]), N.ptr(t["val_p"]), N.ptr(t["raw_s"]), N.ptr(t["raw_p"]), N.ptr(t["G"]), t["ldg"],
+               N.ptr(t["val_rs"]))
+    d_u, d_v, d_ib = _tiled_item_side(u, v, ib, interactions, S, t)
+    return t["loss"], t["pred"], d_u, d_v, t["d_ub"], d_ib
 
 
 def _spmm_rowsum(indptr, indices, values, perm, n_rows, nnz, w, epilogue, accumulate, out, rowsum):

@@ -98,6 +98,25 @@ def warp_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row
     return "warp_fused" if on else None
 
 
+def softmax_tiled_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz, d, shared_negatives, switch=None):
+    """The one-pass kernel of a sampled-softmax step that ``kernel`` left to the generic step -- "softmax_tiled"
+    (csrc/softmax_tiled.hip, ops.softmax_tiled_step: long interaction rows, S in the thousands, Euclidean scores) -- or None: the
+    generic step.  ``loss``: loss_kind's answer ("sampled_softmax": the exact class); a built-in prediction graph in MODE_DOT
+    (cosine counts as dot: the step is fed the normalised operands) or MODE_EUCLIDEAN, one taste, both representations 2-D and
+    equally wide (``d`` that width), ``n_sampled`` given, no shared negatives (their one row goes to csrc/softmax_shared.hip or is
+    expanded for the generic step), then the shape must be covered (ops.step_covers) and the switch on; ``switch``: tuning
+    "softmax_tiled", None reads the library's (ops.SOFTMAX_TILED_DEFAULT: off).  TensorRec._train_step asks only where ``kernel``
+    and ``warp_kernel`` said None: the per-user fused kernel keeps every shape it covers."""
+    if loss != "sampled_softmax" or not engine or engine_mode not in (ops.MODE_DOT, ops.MODE_EUCLIDEAN) or multi or not same_width:
+        return None
+    if n_sampled is None or shared_negatives:
+        return None
+    if not ops.step_covers("softmax_tiled", n_sampled, max_row_nnz, d):
+        return None
+    on = ops.step_switch("softmax_tiled") if switch is None else switch
+    return "softmax_tiled" if on else None
+
+
 def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,
                    n_items, n_sampled, dense_loss, scored_sampler=False):
     """May this batch's step be captured in a HIP graph and replayed?  Single process, no gradient capture, no deterministic grouping;

@@ -435,7 +435,8 @@ class TensorRec(object):
         self.last_route = None        # what predict_top_k did last (route report)
         self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused",
                                       # "softmax_shared", "softmax_full" (step_plan.dense_kernel), "warp_fused" (step_plan.warp_kernel:
-                                      # only with tuning warp_fused = 1);
+                                      # only with tuning warp_fused = 1), "softmax_tiled" (step_plan.softmax_tiled_kernel: only
+                                      # with tuning softmax_tiled = 1);
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -904,6 +905,10 @@ class TensorRec(object):
             if kernel is None:          # the WARP loss: its one-pass step is opt-in (tuning warp_fused), apart from kernel()'s table
                 kernel = step_plan.warp_kernel(step_plan.warp_loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi,
                                                same_width, n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]))
+            if kernel is None:          # the sampled softmax the per-user fused kernel does not cover: the tiled step, opt-in as well
+                kernel = step_plan.softmax_tiled_kernel(step_plan.loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None),
+                                                        multi, same_width, n_sampled_items, inter.max_row_nnz,
+                                                        int(item_repr.shape[-1]), shared)
             if kernel is not None:
                 return self._one_pass_step(kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                            n_sampled_items, want_stats, samples, apply)
@@ -1019,7 +1024,11 @@ class TensorRec(object):
             if kernel == "softmax_fused":
                 out = ops.softmax_fused_step(*operands, samples, loss_graph.temperature,
                                              remove_accidental_hits=loss_graph.remove_accidental_hits, **options)
-            else:                           # "softmax_shared": the one row every user shares
+            elif kernel == "softmax_tiled":
+                out = ops.softmax_tiled_step(*operands, samples, loss_graph.temperature,
+                                             remove_accidental_hits=loss_graph.remove_accidental_hits,
+                                             mode=self.prediction_graph_factory.engine_mode, **options)
+            else:                          # "softmax_shared": the one row every user shares
                 out = ops.softmax_shared_step(*operands, samples[0], loss_graph.temperature, **options)
         return self._finish_fused_step(out[0], out[1], out[2:], u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                        want_stats, apply)
