@@ -717,6 +717,27 @@ int trec_warp_fused_step(const float* U, const float* V, const float* user_bias,
                          int32_t remove_hits, float* loss, float* pred_serial, float* dU, float* d_user_bias,
                          float* coef_samples, float* coef_pairs, int32_t* first, int32_t* sample_hist, int32_t* sample_rank,
                          void* stream);
+/* One training step's user side of the BPR loss in one pass (csrc/bpr_fused.hip): the arguments, the outputs and the coverage of
+ * trec_warp_fused_step without ``first`` -- gather, dU and the rank epilogue are the same code (csrc/user_fused_body.hpp) -- and
+ * with the loss of trec_bpr_fwd / _bwd, or of trec_bpr_adj_fwd / _bwd with remove_hits, at upstream gradient 1:  x_ps = y_s - y_p,
+ * loss_p = (1 / n_sampled) sum_{s kept} softplus(x_ps),  coef_pairs_p = -(1 / n_sampled) sum_{s kept} sigma(x_ps),
+ * coef_samples_us = (1 / n_sampled) sum_{p of u} sigma(x_ps);  one expf, one log1pf and one division per cell (softplus and sigma
+ * share e = exp(-|x|), csrc/sampled_common.hpp); the divisor is n_sampled, also with hits removed.  An interaction with
+ * pos_slot < 0 gets coef_pairs = 0 exactly and adds nothing.  remove_hits != 0: a sample whose item is the column of one of the
+ * user's interactions with pos_slot >= 0 leaves the sums and gets a coefficient of exactly 0 (tested against the user's
+ * interaction ids on chip; the mask is per user).  n_items is not used by the loss.
+ * It replaces trec_pair_score_fwd on both pair lists, trec_bpr_fwd / _bwd and the user side of the pair backward (TF: two
+ * gather_nd score chains, softplus / reduce_mean and their gradients): every item row of a user is gathered once.  No float
+ * atomics and a fixed summation order: two calls give the same bits.  Errors before any launch: TREC_ERR_INVALID for null
+ * pointers, user_bias without d_user_bias or the reverse, sample_rank without sample_hist, null interaction arrays with
+ * remove_hits; TREC_ERR_UNSUPPORTED for a shape trec_bpr_fused_lds_bytes answers with -1 (then run the generic step): the
+ * coverage of trec_softmax_fused_lds_bytes, more bytes.  n_users == 0: TREC_OK, no launch. */
+int trec_bpr_fused_lds_bytes(int32_t n_sampled, int32_t max_interactions_per_user, int32_t d);
+int trec_bpr_fused_step(const float* U, const float* V, const float* user_bias, const float* item_bias,
+                        const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const int32_t* samples,
+                        int64_t n_users, int64_t n_items, int32_t n_sampled, int32_t d, int32_t max_interactions_per_user,
+                        int32_t remove_hits, float* loss, float* pred_serial, float* dU, float* d_user_bias,
+                        float* coef_samples, float* coef_pairs, int32_t* sample_hist, int32_t* sample_rank, void* stream);
 /* The sampled softmax with ONE set of n_sampled negatives shared by every user of the step (csrc/softmax_shared.hip): the sample rows
  * are one gathered [n_sampled, d] matrix Vs with biases sample_bias (nullable) and logit constants sample_c (nullable: 0), and
  * w_us = ((U_u . Vs_s + user_bias_u) + sample_bias_s) inv_temperature + sample_c_s is formed tile by tile on fp32 MFMAs

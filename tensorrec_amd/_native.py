@@ -153,6 +153,9 @@ SIGNATURES = {
     "trec_warp_fused_lds_bytes": [_i32, _i32, _i32],
     "trec_warp_fused_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp],
+    "trec_bpr_fused_lds_bytes": [_i32, _i32, _i32],
+    "trec_bpr_fused_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp],
     "trec_softmax_fused_lds_bytes": [_i32, _i32, _i32],
     "trec_softmax_fused_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _f, _vp, _f, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

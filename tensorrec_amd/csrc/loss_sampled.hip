@@ -16,17 +16,9 @@
 //     backward          d y_p = -(go_p / S) sum_s sigma(y_s - y_p),   d y_us = (1/S) sum_p go_p sigma(y_us - y_p)
 //                       sigma(x) = x >= 0 ? 1 / (1 + e) : e / (1 + e),  e = exp(-|x|)
 //     O(S n_u) like WMRB, and WMRB's loop structure: threads own samples and loop over the staged positives in order.
-#include "sampled_common.hpp"   // the hit rule, ssm_terms, logq_correction, fill_samples, the reductions, the launch forms
+#include "sampled_common.hpp"   // the hit rule, ssm_terms, logq_correction, softplus_f / sigmoid_f, fill_samples, the reductions, the launch forms
 
 #define SL_MAX_POS_LDS 1024        // positives of one user staged per pass (workgroup BPR backward)
-
-__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
-__device__ __forceinline__ float sigmoid_f(float x)
-{
-    const float e = expf(-fabsf(x));
-    return (x >= 0.f ? 1.0f : e) / (1.0f + e);
-}
 
 // ---- the adjusted forms: accidental hits and the logQ correction ---------------------------------------------------------------
 // A sample of user u is a HIT when its item is the column of one of the user's interactions with pos_slot >= 0 (a value <= 0 is no

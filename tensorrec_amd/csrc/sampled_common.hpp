@@ -1,7 +1,7 @@
 // tensorrec_amd/csrc/sampled_common.hpp -- what the per-user sampled-loss family shares: ONE copy of each piece that two files must
 // agree on to the bit (docs/sampled_losses.md).  The family: the loss kernels of csrc/loss.hip (WMRB), csrc/loss_sampled.hip (sampled
 // softmax, BPR), csrc/loss_warp.hip (WARP, with csrc/warp_common.hpp on top of this file) and the one-pass steps
-// csrc/softmax_fused.hip and csrc/warp_fused.hip.  csrc/softmax_shared.hip and csrc/loss_dense.hip take temperature_ok alone.
+// csrc/softmax_fused.hip, csrc/warp_fused.hip and csrc/bpr_fused.hip.  csrc/softmax_shared.hip and csrc/loss_dense.hip take temperature_ok alone.
 #pragma once
 #include "common.hpp"
 #include <math.h>
@@ -83,6 +83,26 @@ __device__ __forceinline__ void ssm_terms(float yp, float M, float Z, float t, f
 
 // the logQ correction of a kept sample: log_s = log S, log_q = log q(item)
 __device__ __forceinline__ float logq_correction(float log_s, float log_q) { return -(log_s + log_q); }
+
+// ---- BPR ----------------------------------------------------------------------------------------------------------------------------
+// one cell x = y_s - y_p: softplus(x) = max(x, 0) + log1p(e), sigma(x) = (x >= 0 ? 1 : e) / (1 + e), e = exp(-|x|); library expf /
+// log1pf and a correctly rounded division.  The forward and the backward kernel of csrc/loss_sampled.hip take one function each
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+__device__ __forceinline__ float sigmoid_f(float x)
+{
+    const float e = expf(-fabsf(x));
+    return (x >= 0.f ? 1.0f : e) / (1.0f + e);
+}
+
+// both from ONE e, for the one-pass step (csrc/bpr_fused.hip): sp == softplus_f(x) and sg == sigmoid_f(x) bit for bit -- the same
+// expressions, e shared
+__device__ __forceinline__ void softplus_sigmoid_f(float x, float& sp, float& sg)
+{
+    const float e = expf(-fabsf(x));
+    sp = fmaxf(x, 0.f) + log1pf(e);
+    sg = (x >= 0.f ? 1.0f : e) / (1.0f + e);
+}
 
 // ---- one user's samples into LDS (four loads per thread in flight, then the four LDS stores: a load -> store loop waits for every
 // load on its own).  As TEXT for the kernels of loss.hip, which held it inline, and as the function the others called ----

@@ -1,5 +1,5 @@
 // tensorrec_amd/csrc/user_fused_body.hpp -- what the one-pass per-user training steps share, as TEXT: csrc/wmrb_fused.hip,
-// csrc/softmax_fused.hip and csrc/warp_fused.hip include it once at file scope for the helpers and the host section (the entry
+// csrc/softmax_fused.hip, csrc/warp_fused.hip and csrc/bpr_fused.hip include it once at file scope for the helpers and the host section (the entry
 // checks, the coverage and the instantiation ladder of their entry points) and three times inside their kernel
 // (template <int ITERS, int RMAX, int SURE, ...>), each time with one USER_FUSED_PART defined:
 //     USER_FUSED_PART 1   the prologue: thread indices, the sample ids, the user's interaction range, the user without interactions

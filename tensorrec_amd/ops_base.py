@@ -898,14 +898,15 @@ GROUP_BINNED_MIN_PAIRS = int(_os.environ.get("TREC_BINNED_MIN_PAIRS", 1 << 22)) 
 
 def step_switch(name):
     """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT,
-    "softmax_full" to SOFTMAX_FULL_DEFAULT, "warp_fused" to WARP_FUSED_DEFAULT, "softmax_tiled" to SOFTMAX_TILED_DEFAULT.)"""
+    "softmax_full" to SOFTMAX_FULL_DEFAULT, "warp_fused" to WARP_FUSED_DEFAULT, "softmax_tiled" to SOFTMAX_TILED_DEFAULT, "bpr_fused" to
+    BPR_FUSED_DEFAULT.)"""
     default = {"softmax_shared": SOFTMAX_SHARED_DEFAULT, "softmax_full": SOFTMAX_FULL_DEFAULT, "warp_fused": WARP_FUSED_DEFAULT,
-               "softmax_tiled": SOFTMAX_TILED_DEFAULT}.get(name, 1)
+               "softmax_tiled": SOFTMAX_TILED_DEFAULT, "bpr_fused": BPR_FUSED_DEFAULT}.get(name, 1)
     return N.load().trec_get_tuning(name.encode(), default) != 0
 
 
 def step_covers(kernel, n_sampled, max_row_nnz, d):
-    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_tiled", "warp_fused", "softmax_shared") cover this shape?  The ONE
+    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_tiled", "warp_fused", "bpr_fused", "softmax_shared") cover this shape?  The ONE
     statement of the coverage: the native library's shape query (host arithmetic, needs no GPU); step_plan.kernel and the
     ``*_supported`` functions below both ask here."""
     if kernel == "softmax_shared":         # (the interactions do not restrict it: the positives are O(P) work on K3's scores)
@@ -995,7 +996,7 @@ def _gather_over_users(interactions, coef, v):
 
 
 def _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks):
-    """The item side of a one-pass fused step (wmrb_fused_step, softmax_fused_step, warp_fused_step): d item_in = G^T . user_in over both pair lists,
+    """The item side of a one-pass fused step (wmrb_fused_step, softmax_fused_step, warp_fused_step, bpr_fused_step): d item_in = G^T . user_in over both pair lists,
     d b_i = per-item sums of the coefficients -- the static transposed structure for the interactions, the binned or ranked grouping
     (_fused_sample_grouping) for the samples, the packed K1 gather with the row-sum epilogue.  Returns (d_v, d_ib)."""
     n_users, n_items = interactions.shape
@@ -1117,6 +1118,32 @@ def warp_fused_step(user_in, item_in, user_bias, item_bias, interactions, sample
     d_v, d_ib = _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks)
     out = (loss, pred, d_u, d_v, d_ub, d_ib)
     return out + (first,) if return_first else out
+
+
+BPR_FUSED_DEFAULT = 0            # tuning "bpr_fused" when nobody set it: the route is opt-in (docs/sampled_losses.md, "The one-pass fused step (BPR)")
+
+
+def bpr_fused_supported(n_sampled, interactions, d):
+    """Can the one-pass BPR step (csrc/bpr_fused.hip) run this shape, and is tuning ``bpr_fused`` on (it defaults to off)?"""
+    return _step_supported("bpr_fused", n_sampled, interactions, d)
+
+
+def bpr_fused_step(user_in, item_in, user_bias, item_bias, interactions, samples, remove_accidental_hits=False):
+    """One BPR step for dot scores on (user_in, item_in), upstream gradient 1: warp_fused_step with the loss of bpr_loss
+    (``remove_accidental_hits`` as there).  Returns (loss [P+], pred_serial [P], d user_in, d item_in, d user_bias, d item_bias);
+    the item side is wmrb_fused_step's.  Every kept sample of a user with a positive has a coefficient > 0 (sigma never reaches 0
+    short of underflow): the item side sees all sampled pairs but the hits."""
+    u, v, ub, ib, loss, pred, d_u, d_ub, coef_s, coef_p, samples, xs, (binned_bytes, ws32, ranks) = \
+        _fused_step_buffers(user_in, item_in, user_bias, item_bias, interactions, samples)
+    n_users, n_items = interactions.shape
+    S, d = int(samples.shape[1]), u.shape[1]
+    with _timed("bpr_fused_step"):
+        N.call("trec_bpr_fused_step", N.ptr(u), N.ptr(v), N.ptr(ub), N.ptr(ib), N.ptr(interactions.indptr),
+               N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot), N.ptr(samples), n_users, n_items, S, d,
+               int(interactions.max_row_nnz), 1 if remove_accidental_hits else 0, N.ptr(loss), N.ptr(pred), N.ptr(d_u), N.ptr(d_ub),
+               N.ptr(coef_s), N.ptr(coef_p), N.ptr(ws32), N.ptr(ranks))
+    d_v, d_ib = _fused_item_side(u, v, ib, interactions, xs, S, coef_s, coef_p, loss, binned_bytes, ws32, ranks)
+    return loss, pred, d_u, d_v, d_ub, d_ib
 
 
 SOFTMAX_SHARED_DEFAULT = 1       # tuning "softmax_shared" when nobody set it (docs/sampled_losses.md, "Shared negatives": the measurement)

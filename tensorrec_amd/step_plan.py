@@ -8,7 +8,7 @@ _CoopStep.plan and TensorRec._graph_eligible gather the inputs; the shapes a ker
 from collections import namedtuple
 
 from . import ops
-from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph, SoftmaxDenseLossGraph, WARPLossGraph
+from .loss_graphs import WMRBLossGraph, BalancedWMRBLossGraph, SampledSoftmaxLossGraph, SoftmaxDenseLossGraph, WARPLossGraph, BPRLossGraph
 
 Switches = namedtuple("Switches", "wmrb_fused wmrb_tiled softmax_fused softmax_shared fit_step_coop")
 # only the exact built-in classes have a kind: a subclass may override anything the kernels restate
@@ -96,6 +96,26 @@ def warp_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row
         return None
     on = ops.step_switch("warp_fused") if switch is None else switch
     return "warp_fused" if on else None
+
+
+def bpr_loss_kind(loss_graph):
+    """"bpr" for an instance of exactly BPRLossGraph, None for everything else (a subclass may override anything the kernel
+    restates).  Apart from ``kernel``'s table, as warp_loss_kind is: the one-pass BPR step is opt-in."""
+    return "bpr" if type(loss_graph) is BPRLossGraph else None
+
+
+def bpr_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz, d, switch=None):
+    """The one-pass kernel of a training step under the BPR loss -- "bpr_fused" (csrc/bpr_fused.hip, ops.bpr_fused_step) -- or None:
+    the generic step.  ``loss``: bpr_loss_kind's answer; the guards are warp_kernel's -- a built-in prediction graph in MODE_DOT
+    (cosine counts as dot: the step is fed the normalised operands), one taste, both representations 2-D and equally wide (``d``
+    that width), ``n_sampled`` given --, then the shape must be covered (ops.step_covers) and the switch on; ``switch``: tuning
+    "bpr_fused", None reads the library's (ops.BPR_FUSED_DEFAULT: off)."""
+    if loss != "bpr" or not engine or engine_mode != ops.MODE_DOT or multi or not same_width or n_sampled is None:
+        return None
+    if not ops.step_covers("bpr_fused", n_sampled, max_row_nnz, d):
+        return None
+    on = ops.step_switch("bpr_fused") if switch is None else switch
+    return "bpr_fused" if on else None
 
 
 def softmax_tiled_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, max_row_nnz, d, shared_negatives, switch=None):

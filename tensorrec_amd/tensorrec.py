@@ -436,7 +436,8 @@ class TensorRec(object):
         self.last_step_kernel = None  # which one-pass kernel the last training step took: "wmrb_fused", "wmrb_tiled", "softmax_fused",
                                       # "softmax_shared", "softmax_full" (step_plan.dense_kernel), "warp_fused" (step_plan.warp_kernel:
                                       # only with tuning warp_fused = 1), "softmax_tiled" (step_plan.softmax_tiled_kernel: only
-                                      # with tuning softmax_tiled = 1);
+                                      # with tuning softmax_tiled = 1), "bpr_fused" (step_plan.bpr_kernel: only with tuning
+                                      # bpr_fused = 1);
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -905,6 +906,9 @@ class TensorRec(object):
             if kernel is None:          # the WARP loss: its one-pass step is opt-in (tuning warp_fused), apart from kernel()'s table
                 kernel = step_plan.warp_kernel(step_plan.warp_loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi,
                                                same_width, n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]))
+            if kernel is None:          # the BPR loss: opt-in as well (tuning bpr_fused)
+                kernel = step_plan.bpr_kernel(step_plan.bpr_loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None), multi,
+                                              same_width, n_sampled_items, inter.max_row_nnz, int(item_repr.shape[-1]))
             if kernel is None:          # the sampled softmax the per-user fused kernel does not cover: the tiled step, opt-in as well
                 kernel = step_plan.softmax_tiled_kernel(step_plan.loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None),
                                                         multi, same_width, n_sampled_items, inter.max_row_nnz,
@@ -1017,6 +1021,8 @@ class TensorRec(object):
             out = ops.wmrb_tiled_step(*operands, samples, balanced=loss_graph.balanced, mode=self.prediction_graph_factory.engine_mode)
         elif kernel == "warp_fused":
             out = ops.warp_fused_step(*operands, samples, remove_accidental_hits=loss_graph.remove_accidental_hits)
+        elif kernel == "bpr_fused":
+            out = ops.bpr_fused_step(*operands, samples, remove_accidental_hits=loss_graph.remove_accidental_hits)
         else:
             log_q = getattr(self.sampler, 'log_q', None)
             options = dict(sample_log_q=log_q(self._store.device) if callable(log_q) else None,
