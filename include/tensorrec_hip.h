@@ -422,7 +422,8 @@ int trec_score_gemm_refine_candidates_marked(const void* users_bf16, const void*
  * trec_pair_score_exact their reference-chain scores (biases included),
  * trec_topk_euclid_certify orders them by (score desc, id asc), writes the first k, and flags the users for whom an item OUTSIDE the
  * kc could still reach the first k places (score upper bound from the kc-th largest g and the largest item bias; csrc/euclid_topk.hip):
- * those are re-done on the exact fp32 MFMA path.  item_gstats: trec_score_prep_filter's maxima with bias = -r / 2. */
+ * those are re-done on the exact fp32 MFMA path, and so is a user with a hole (id < 0) or a NaN score among the kc.  item_gstats:
+ * trec_score_prep_filter's maxima with bias = -r / 2. */
 int trec_topk_euclid_certify(const int32_t* cand_idx, const float* cand_g, const float* exact, int32_t kc, int32_t k,
                              const float* user_sq, const float* user_bias, const float* item_gstats, const float* bias_max,
                              int32_t kdim, int64_t n_users, float* out_vals, int32_t* out_idx, int32_t* flag,

@@ -54,7 +54,11 @@ __global__ __launch_bounds__(256) void euclid_certify_kernel(const int32_t* __re
         if (j < kc) {
             const int32_t id = cand_idx[u * kc + j];
             if (id < 0) hole = true;
-            else key[j] = merge_key(exact[u * kc + j], id);
+            else {
+                const float s = exact[u * kc + j];
+                if (s != s) hole = true;                                    // a NaN score: its key sorts FIRST (or last), so tk alone never sees it
+                key[j] = merge_key(s, id);
+            }
         }
     }
     // insertion sort, descending keys = (score desc, id asc): kc <= EC_MAX entries in registers
