@@ -83,13 +83,20 @@ int trec_spmv_csr(const int64_t* indptr, const int32_t* indices, const float* va
  * (own[row,:] - W[col,:]) instead of W[col,:] -- the Euclidean pair gradient, prediction_graphs.py:105-117
  * differentiated, with the coefficients of trec_pair_euclid_coef as values.  out_rowsum (nullable): sums of the rows'
  * values.  accumulate != 0: out += (and out_rowsum +=).  workspace: trec_csr_split_workspace_bytes(nnz, d) bytes.
- * d: a multiple of 4 up to 1024 (float4 lanes), or any width up to 256 (single-column lanes).                     */
+ * d: a multiple of 4 up to 1024 (float4 lanes), or any width up to 256 (single-column lanes).
+ * The threshold is the tuning "split_t" (default 2048), allowed range split_t >= 2: a row of more than split_t non-zeros
+ * is cut into chunks of split_t / 2 (rounded down), each chunk an fmaf chain from zero in CSR order, the partials added in
+ * chunk order onto out (accumulate) or onto zero; out_rowsum is the same chain of plain adds.  With split_t < 2 (empty
+ * chunks) trec_csr_split_workspace_bytes returns -1 and trec_spmm_csr_split / trec_spmv_csr_split return
+ * TREC_ERR_INVALID on the host, before anything is launched.                                                          */
 int64_t trec_csr_split_workspace_bytes(int64_t nnz, int32_t d);
 int trec_spmm_csr_split(const int64_t* indptr, const int32_t* indices, const float* values, const int32_t* val_perm,
                         const void* packed_entries, int64_t n_rows, int64_t nnz, const float* W, int32_t d,
                         const float* own, int32_t accumulate, float* out, float* out_rowsum, void* workspace,
                         int64_t workspace_bytes, void* stream);
-/* trec_spmv_csr with the same treatment of long rows (workspace: trec_csr_split_workspace_bytes(nnz, 1)) */
+/* trec_spmv_csr with the same treatment of long rows (workspace: trec_csr_split_workspace_bytes(nnz, 1)); the same range
+ * of split_t (>= 2).  Rows at or below the threshold are trec_spmv_csr's sums bit for bit; a chunk of a longer row is summed
+ * by 64 strided lanes (fmaf with beta, plain adds without) and a butterfly, the chunk sums added in chunk order from zero. */
 int trec_spmv_csr_split(const int64_t* indptr, const int32_t* indices, const float* values, const int32_t* val_perm,
                         int64_t n_rows, int64_t nnz, const float* beta, float* out, void* workspace,
                         int64_t workspace_bytes, void* stream);

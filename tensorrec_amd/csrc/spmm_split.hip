@@ -21,6 +21,9 @@
 namespace {
 
 constexpr int SPLIT_T_DEFAULT = 2048;
+// the tuning knob split_t: chunks hold split_t / 2 non-zeros, so 1 would make them empty (the plan kernel divides by the chunk
+// length) and 0 divides in plan_layout -- the entry points refuse anything below 2 on the host, before a launch
+constexpr int SPLIT_T_MIN = 2;
 
 struct SplitPlan {
     int32_t* hdr;          // [0] chunks handed out, [1] long rows listed
@@ -403,7 +406,9 @@ static int make_plan(const int64_t* indptr, int64_t n_rows, int64_t nnz, int d, 
 extern "C" int64_t trec_csr_split_workspace_bytes(int64_t nnz, int32_t d)
 {
     if (nnz < 0 || d < 1) return -1;
-    return plan_layout(nnz, d, trec_get_tuning("split_t", SPLIT_T_DEFAULT), nullptr, nullptr);
+    const int split_t = trec_get_tuning("split_t", SPLIT_T_DEFAULT);
+    if (split_t < SPLIT_T_MIN) return -1;
+    return plan_layout(nnz, d, split_t, nullptr, nullptr);
 }
 
 extern "C" int trec_spmm_csr_split(const int64_t* indptr, const int32_t* indices, const float* values,
@@ -416,9 +421,10 @@ extern "C" int trec_spmm_csr_split(const int64_t* indptr, const int32_t* indices
     TREC_REQUIRE(d >= 1 && ((d % 4 == 0 && d <= 1024) || d <= 256),
                  "trec_spmm_csr_split: d must be a multiple of 4 up to 1024, or any value up to 256");
     TREC_REQUIRE(n_rows >= 0 && nnz >= 0, "trec_spmm_csr_split: bad sizes");
+    const int split_t = trec_get_tuning("split_t", SPLIT_T_DEFAULT);
+    TREC_REQUIRE(split_t >= SPLIT_T_MIN, "trec_spmm_csr_split: the tuning split_t must be at least 2 (chunks of split_t / 2 non-zeros)");
     if (n_rows == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int split_t = trec_get_tuning("split_t", SPLIT_T_DEFAULT);
     SplitPlan plan;
     int rc = make_plan(indptr, n_rows, nnz, d, workspace, workspace_bytes, split_t, &plan, st, "trec_spmm_csr_split(plan)");
     if (rc) return rc;
@@ -462,9 +468,10 @@ extern "C" int trec_spmv_csr_split(const int64_t* indptr, const int32_t* indices
     TREC_REQUIRE(indptr && out, "trec_spmv_csr_split: null pointer");
     TREC_REQUIRE(nnz == 0 || values, "trec_spmv_csr_split: null values with nnz != 0");
     TREC_REQUIRE(!beta || nnz == 0 || indices, "trec_spmv_csr_split: beta needs indices");
+    const int split_t = trec_get_tuning("split_t", SPLIT_T_DEFAULT);
+    TREC_REQUIRE(split_t >= SPLIT_T_MIN, "trec_spmv_csr_split: the tuning split_t must be at least 2 (chunks of split_t / 2 non-zeros)");
     if (n_rows == 0) return TREC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int split_t = trec_get_tuning("split_t", SPLIT_T_DEFAULT);
     SplitPlan plan;
     int rc = make_plan(indptr, n_rows, nnz, 1, workspace, workspace_bytes, split_t, &plan, st, "trec_spmv_csr_split(plan)");
     if (rc) return rc;

@@ -81,6 +81,8 @@ _SPLIT_MEAN = 1700
 
 def _split_workspace(nnz, d, dev):
     nbytes = N.query("trec_csr_split_workspace_bytes", int(nnz), int(d))
+    if nbytes < 0:
+        raise ValueError("split gather: no workspace for nnz=%d, d=%d (the tuning split_t must be at least 2)" % (nnz, d))
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
 
 
