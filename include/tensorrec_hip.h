@@ -779,6 +779,38 @@ int trec_softmax_shared_grads(const float* U, const float* Vs, const float* user
                               float* d_sample_bias, void* stream);
 int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int64_t* order, const float* dVs, const float* d_sample_bias,
                                 int32_t n_sampled, int32_t d, int64_t n_items, float* dV, float* d_item_bias, void* stream);
+/* The same step with ACCIDENTAL HITS REMOVED (it replaces the chain gather -> trec_pair_score_fwd over [n_users, n_sampled] pairs ->
+ * trec_sampled_softmax_adj_fwd / _bwd with remove_hits -> autograd on the table that repeats the shared row; TF's counterpart is
+ * tf.nn.sampled_softmax_loss(remove_accidental_hits=True)): column s is a hit for user u when the sampled id
+ * is the item of an interaction of u with pos_slot >= 0; a hit is left out of M[u] and Z[u] and its P_us is exactly 0.f.  A user
+ * whose samples are all hits has M = -inf, Z = 0, and trec_softmax_shared_positives then writes loss = 0, d_pred = -0, tK = 0 for
+ * it (its m = w_p, a = 1, b = exp(-inf) = 0, D = 1): that entry point is used unchanged.  The columns -- Vs, sample_bias, sample_c --
+ * are handed over in SORTED id order (sorted_ids [n_sampled] ascending, duplicates adjacent), so a user's hits are ascending,
+ * disjoint column ranges; sample_c keeps the full n_sampled in -log(n_sampled q).  No workspace of size [n_users, n_sampled], no
+ * float atomics, fixed summation orders, nothing read on the host.
+ *   _hit_ranges  one thread per user: for every interaction with pos_slot >= 0 whose item occurs in sorted_ids the range [lo, hi) of
+ *                its columns, as int32 pairs compacted at hit_rng[2 (indptr[u] + j)], j < hit_cnt[u] (hit_rng holds nnz pairs,
+ *                hit_cnt n_users counts).  x_item must ascend within a row without repeats (CSR with sorted, summed indices).
+ *   _hits_stats  trec_softmax_shared_stats with the masked columns entering as -inf.
+ *   _hits_grads  trec_softmax_shared_grads with the masked P_us a literal 0.f.  The role with the samples resident finds the users
+ *                to mask for column s in the transposed positives: indptr_tp [n_items + 1], users_tp -- per item the users,
+ *                ascending, whose interaction with it has pos_slot >= 0; ids outside [0, n_items) mask nobody.  n_slices and
+ *                workspace as in trec_softmax_shared_grads.
+ * trec_softmax_shared_scatter then takes sorted_ids with order = 0 ... n_sampled - 1.
+ * Errors before any launch: TREC_ERR_INVALID for null pointers, n_sampled < 1, d outside trec_softmax_shared_supported, an
+ * inv_temperature that is not finite and > 0, a wrong n_slices; n_users == 0 returns TREC_OK without a launch. */
+int trec_softmax_shared_hit_ranges(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot, const int32_t* sorted_ids,
+                                   int64_t n_users, int32_t n_sampled, int32_t* hit_rng, int32_t* hit_cnt, void* stream);
+int trec_softmax_shared_hits_stats(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                                   const float* sample_c, const int64_t* indptr, const int32_t* hit_rng, const int32_t* hit_cnt,
+                                   int64_t n_users, int32_t n_sampled, int32_t d, float inv_temperature, float* M, float* Z,
+                                   void* stream);
+int trec_softmax_shared_hits_grads(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                                   const float* sample_c, const float* M, const float* tK, const int64_t* indptr,
+                                   const int32_t* hit_rng, const int32_t* hit_cnt, const int32_t* sorted_ids, const int64_t* indptr_tp,
+                                   const int32_t* users_tp, int64_t n_items, int64_t n_users, int32_t n_sampled, int32_t d,
+                                   float inv_temperature, int32_t n_slices, float* workspace, float* dU, float* dVs,
+                                   float* d_sample_bias, void* stream);
 /* The positives of the FULL softmax over the catalogue, loss_p = log sum_i exp((y_ui - y_up) inv_temperature), for the step that
  * streams the item representation itself through _stats / _grads above (Vs = V, sample_bias = item_bias, sample_c = NULL, n_sampled =
  * n_items; no scatter): with w = y inv_temperature, M[u] = max_i w_ui and Z[u] = sum_i exp(w_ui - M[u]) from _stats -- the positives

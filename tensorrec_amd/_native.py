@@ -165,6 +165,10 @@ SIGNATURES = {
     "trec_softmax_shared_positives": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp],
     "trec_softmax_shared_grads": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f, _i32, _vp, _vp, _vp, _vp, _vp],
     "trec_softmax_shared_scatter": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp],
+    "trec_softmax_shared_hit_ranges": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "trec_softmax_shared_hits_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp],
+    "trec_softmax_shared_hits_grads": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _f,
+                                       _i32, _vp, _vp, _vp, _vp, _vp],
     "trec_softmax_full_positives": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp, _vp, _vp],
     "trec_wmrb_tiled_lds_bytes": [_i32, _i32, _i32],
     "trec_wmrb_tiled_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,

@@ -16,6 +16,7 @@
 //             operations in the same order in all three roles, so it is the same float); partial [S, d] products and row sums per
 //             slice, added in slice order by reduce_slices_kernel.
 // Every sum has a fixed order and there are no float atomics: a call is deterministic.
+// shared_tile_hits_kernel<KT, ROLE> is the same kernel with accidental hits removed; the two share one body, softmax_shared_body.hpp.
 #include "sampled_common.hpp"   // temperature_ok
 #include <math.h>
 
@@ -46,209 +47,73 @@ struct SharedParams {
 
 __device__ __forceinline__ int ss_cd_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
+// Accidental hits removed (HITS): the columns arrive SORTED by sample id, so the hits of a user are ascending, disjoint column ranges
+// (shared_hit_ranges_kernel) and the users that have a sampled item as a positive are an ascending list (the transposed positives).
+//   users resident    hit_rng [nnz][2] / hit_cnt [n_users]: user u's ranges [lo, hi) of sorted columns, compacted at indptr[u]
+//   samples resident  sorted_ids [S], indptr_tp [n_items + 1], users_tp: the users, ascending, whose interaction with the item has
+//                     pos_slot >= 0
+struct SharedHits {
+    const int64_t* indptr;
+    const int32_t* hit_rng;
+    const int32_t* hit_cnt;
+    const int32_t* sorted_ids;
+    const int64_t* indptr_tp;
+    const int32_t* users_tp;
+    int64_t n_items;
+};
+
 // (KT = 128 with the product accumulators needs more than 256 registers: one workgroup per CU there instead of spills)
 template <int KT, int ROLE>
 __global__ __launch_bounds__(256, (KT >= 128 && ROLE != SS_STATS) ? 1 : 2) void shared_tile_kernel(SharedParams p)
 {
-    constexpr int BN = 32;                  // streamed rows per tile = one 32 x 32 MFMA block
-    constexpr int RB = KT * 4;              // bytes per LDS row
-    constexpr int CH = RB / 16;             // 16-byte chunks per row
-    constexpr int KS = KT / 2;              // MFMA k-steps of the score
-    constexpr int CB = KT / 32;             // 32-column blocks of the product
-    constexpr int TILE_BYTES = BN * RB;
-    constexpr int NSLOT = BN * CH / 256;    // 16-byte staging slots per thread per tile
-    constexpr int NSIDE = 3;                // per streamed row: bias, then c (samples) or M, tK (users)
-    static_assert(NSLOT >= 1, "tile too small for 256 threads");
-    extern __shared__ __attribute__((aligned(16))) char ssmem[];
-    float* side = (float*)(ssmem + 2 * TILE_BYTES);        // [2][NSIDE][BN]
+#define SS_HITS 0
+#include "softmax_shared_body.hpp"
+#undef SS_HITS
+}
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
-    const int rblock = blockIdx.x % p.n_rblocks;
-    const int slice = blockIdx.x / p.n_rblocks;
-    const int64_t row = ((int64_t)rblock * 4 + wave) * 32 + l31;
-    const bool row_ok = row < p.n_res;
-    const int64_t src = row_ok ? row : 0;
-    const int d = p.d;
-    const int64_t t_begin = (int64_t)slice * p.slice_len;
-    const int64_t t_end = (t_begin + p.slice_len < p.n_str) ? t_begin + p.slice_len : p.n_str;
-    const int n_tiles = (int)((t_end - t_begin + BN - 1) / BN);
-    const float inv_t = p.inv_t;
+// the same with accidental hits removed
+template <int KT, int ROLE>
+__global__ __launch_bounds__(256, (KT >= 128 && ROLE != SS_STATS) ? 1 : 2) void shared_tile_hits_kernel(SharedParams p, SharedHits h)
+{
+#define SS_HITS 1
+#include "softmax_shared_body.hpp"
+#undef SS_HITS
+}
 
-    float rff[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        const int k = 2 * ks + half;
-        rff[ks] = (k < d) ? p.R[src * d + k] : 0.f;
-    }
-    const float rb = p.r_bias ? p.r_bias[src] : 0.f;
-    float rM = 0.f, rK = 0.f, rc = 0.f;
-    if (ROLE == SS_DU) { rM = p.M[src]; rK = row_ok ? p.tK[src] : 0.f; }
-    if (ROLE == SS_DV) rc = p.cs ? p.cs[src] : 0.f;
-
-    // ---- staging: slot q = i * 256 + tid -> (row, physical 16-byte chunk), XOR-swizzled as in score_rank.hip; chunks past d are zeros
-    int slot_row[NSLOT], slot_src[NSLOT];
-#pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
-        const int q = i * 256 + tid;
-        const int r = q / CH, pc = q % CH;
-        const int sw = (CH >= 16) ? (r & 15) : ((CH == 8) ? ((r >> 1) & 7) : 0);
-        slot_row[i] = r;
-        slot_src[i] = (pc ^ sw) * 16;
-    }
-    u32x4 stage[NSLOT];
-    float side_v[NSIDE] = {0.f, 0.f, 0.f};
-    auto stage_issue = [&](int tile) {
-        const int64_t row0 = t_begin + (int64_t)tile * BN;
-        if (tid < BN) {
-            int64_t g = row0 + tid;
-            if (g >= p.n_str) g = p.n_str - 1;              // clamped rows are masked below
-            side_v[0] = p.t_bias ? p.t_bias[g] : 0.f;
-            if (ROLE == SS_DV) { side_v[1] = p.M[g]; side_v[2] = p.tK[g]; }
-            else side_v[1] = p.cs ? p.cs[g] : 0.f;
+// One thread per user: the sorted-column ranges [lo, hi) that hold the item of one of the user's interactions with pos_slot >= 0,
+// written compacted, ascending and disjoint (x_item ascends within a row, without repeats) at hit_rng[indptr[u] + j], their number
+// into hit_cnt[u].  An interaction with pos_slot < 0 is no hit; duplicate sample ids are one range.
+__global__ __launch_bounds__(256) void shared_hit_ranges_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ x_item,
+                                                                const int32_t* __restrict__ pos_slot,
+                                                                const int32_t* __restrict__ sorted_ids, int64_t n_users, int S,
+                                                                int32_t* __restrict__ hit_rng, int32_t* __restrict__ hit_cnt)
+{
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= n_users) return;
+    const int64_t b = indptr[u], e = indptr[u + 1];
+    int cnt = 0;
+    for (int64_t q = b; q < e; ++q) {
+        if (pos_slot[q] < 0) continue;
+        const int32_t item = x_item[q];
+        int lo = 0, hi = S;
+        while (lo < hi) {
+            const int mid = (int)(((int64_t)lo + hi) >> 1);
+            if (sorted_ids[mid] < item) lo = mid + 1;
+            else hi = mid;
         }
-#pragma unroll
-        for (int i = 0; i < NSLOT; ++i) {
-            int64_t g = row0 + slot_row[i];
-            if (g >= p.n_str) g = p.n_str - 1;
-            const u32x4 zero = {0u, 0u, 0u, 0u};
-            stage[i] = (slot_src[i] < d * 4) ? *(const u32x4*)((const char*)p.T + g * (int64_t)d * 4 + slot_src[i]) : zero;
+        if (lo >= S || sorted_ids[lo] != item) continue;
+        int l2 = lo + 1;
+        hi = S;
+        while (l2 < hi) {
+            const int mid = (int)(((int64_t)l2 + hi) >> 1);
+            if (sorted_ids[mid] <= item) l2 = mid + 1;
+            else hi = mid;
         }
-    };
-    auto stage_commit = [&](int buf) {
-        if (tid < BN) {
-#pragma unroll
-            for (int j = 0; j < NSIDE; ++j) side[(buf * NSIDE + j) * BN + tid] = side_v[j];
-        }
-#pragma unroll
-        for (int i = 0; i < NSLOT; ++i) *(u32x4*)(ssmem + buf * TILE_BYTES + (i * 256 + tid) * 16) = stage[i];
-    };
-
-    f32x16 prod[ROLE == SS_STATS ? 1 : CB];
-    if (ROLE != SS_STATS) {
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) prod[cb][r] = 0.f;
+        hit_rng[2 * (b + cnt)] = lo;
+        hit_rng[2 * (b + cnt) + 1] = l2;
+        ++cnt;
     }
-    float run_m = -INFINITY, run_z = 0.f;    // SS_STATS
-    float psum = 0.f;                        // SS_DV: this lane's share of d b_s
-
-    stage_issue(0);
-    stage_commit(0);
-    __syncthreads();
-    for (int t = 0; t < n_tiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < n_tiles) stage_issue(t + 1);
-        const char* tile = ssmem + buf * TILE_BYTES;
-        const char* rowp = tile + l31 * RB;
-        const int sw = (CH >= 16) ? (l31 & 15) : ((CH == 8) ? ((l31 >> 1) & 7) : 0);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if (2 * ks < d) {                                                  // (uniform: the padded k-steps add exact zeros)
-                const int k = 2 * ks + half;
-                const float tf = *(const float*)(rowp + (((k >> 2) ^ sw) * 16) + (k & 3) * 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tf, rff[ks], acc, 0, 0, 0);
-            }
-        }
-        const float* sd = side + buf * NSIDE * BN;
-        const int64_t loc0 = t_begin + (int64_t)t * BN;
-        const int rows_left = (int)((p.n_str - loc0 < BN) ? (p.n_str - loc0) : BN);
-        // ---- w of my resident row against the streamed rows ss_cd_row(r, half): ((dot + b_u) + b_s) t + c_s in every role
-        float tile_m = -INFINITY;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const f32x4 tb4 = *(const f32x4*)(sd + 8 * q4 + 4 * half);
-            const f32x4 s14 = *(const f32x4*)(sd + BN + 8 * q4 + 4 * half);
-            f32x4 s24 = {0.f, 0.f, 0.f, 0.f};
-            if (ROLE == SS_DV) s24 = *(const f32x4*)(sd + 2 * BN + 8 * q4 + 4 * half);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool valid = 8 * q4 + 4 * half + e < rows_left;
-                float v = acc[4 * q4 + e];
-                if (ROLE == SS_DV) {
-                    v = (v + tb4[e]) + rb;
-                    v = fmaf(v, inv_t, rc);
-                    v = valid ? s24[e] * expf(v - s14[e]) : 0.f;
-                    psum += v;
-                } else {
-                    v = (v + rb) + tb4[e];
-                    v = fmaf(v, inv_t, s14[e]);
-                    if (ROLE == SS_DU) v = valid ? rK * expf(v - rM) : 0.f;
-                    else {
-                        v = valid ? v : -INFINITY;
-                        tile_m = fmaxf(tile_m, v);
-                    }
-                }
-                acc[4 * q4 + e] = v;
-            }
-        }
-        if (ROLE == SS_STATS) {
-            if (tile_m > -INFINITY) {                        // (a half-wave whose columns all lie past S adds nothing)
-                if (tile_m > run_m) {
-                    run_z = run_z * expf(run_m - tile_m);    // (first tile: 0 * exp(-inf) = 0)
-                    run_m = tile_m;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) run_z += expf(acc[r] - run_m);
-            }
-        } else {
-            // ---- product: C[column cb * 32 + i][resident j] += sum_r T[row ss_cd_row(r, k)][column] P[k][j], k = half
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                if (cb * 32 < d) {
-                    const int k = cb * 32 + l31;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = ss_cd_row(r, half);
-                        const int swr = (CH >= 16) ? (rr & 15) : ((CH == 8) ? ((rr >> 1) & 7) : 0);
-                        const float a = *(const float*)(tile + rr * RB + (((k >> 2) ^ swr) * 16) + (k & 3) * 4);
-                        prod[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, acc[r], prod[cb], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        if (t + 1 < n_tiles) stage_commit(buf ^ 1);
-        __syncthreads();
-    }
-
-    if (ROLE == SS_STATS) {
-        const float om = __shfl_xor(run_m, 32, 64), oz = __shfl_xor(run_z, 32, 64);
-        // half 0 first, then half 1, in both lanes: M = max, Z = z0 exp(m0 - M) + z1 exp(m1 - M); an empty half adds an exact 0
-        const float m0 = half ? om : run_m, z0 = half ? oz : run_z;
-        const float m1 = half ? run_m : om, z1 = half ? run_z : oz;
-        const float Mx = fmaxf(m0, m1);
-        const float a0 = (m0 > -INFINITY) ? z0 * expf(m0 - Mx) : 0.f;
-        const float a1 = (m1 > -INFINITY) ? z1 * expf(m1 - Mx) : 0.f;
-        if (row_ok && half == 0) { p.out_M[row] = Mx; p.out_Z[row] = a0 + a1; }
-        return;
-    }
-    // ---- the product of my resident row: prod[cb][4 q + e] is column cb * 32 + 8 q + 4 half + e
-    float* orow = p.out + ((ROLE == SS_DV ? (int64_t)slice * p.n_res : 0) + src) * d;
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) {
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const int c0 = cb * 32 + 8 * q4 + 4 * half;
-            if (row_ok && c0 < d) {
-                f32x4 o = {prod[cb][4 * q4], prod[cb][4 * q4 + 1], prod[cb][4 * q4 + 2], prod[cb][4 * q4 + 3]};
-                if (ROLE == SS_DU) {
-                    const f32x4 have = *(const f32x4*)(orow + c0);
-                    o = have + o;
-                }
-                *(f32x4*)(orow + c0) = o;
-            }
-        }
-    }
-    if (ROLE == SS_DV) {
-        const float other = __shfl_xor(psum, 32, 64);
-        if (row_ok && half == 0 && p.out_sum) p.out_sum[(int64_t)slice * p.n_res + row] = psum + other;
-    }
+    hit_cnt[u] = cnt;
 }
 
 // out[i] = the slices' partials added in slice order
@@ -362,9 +227,15 @@ extern "C" int trec_softmax_shared_slices(int64_t n_users, int32_t n_sampled, in
 }
 
 template <int KT, int ROLE>
-static int ss_launch(const SharedParams& p, int n_slices, hipStream_t st)
+static int ss_launch(const SharedParams& p, int n_slices, hipStream_t st, const SharedHits* h)
 {
     constexpr int LDS = 2 * 32 * KT * 4 + 2 * 3 * 32 * 4;
+    if (h) {                                                  // accidental hits removed
+        auto kern = shared_tile_hits_kernel<KT, ROLE>;
+        if (LDS > 32 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.n_rblocks * (unsigned)n_slices), dim3(256), LDS, st, p, *h);
+        return trec_check_launch("trec_softmax_shared_hits");
+    }
     auto kern = shared_tile_kernel<KT, ROLE>;
     if (LDS > 32 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     hipLaunchKernelGGL(kern, dim3((unsigned)p.n_rblocks * (unsigned)n_slices), dim3(256), LDS, st, p);
@@ -372,11 +243,11 @@ static int ss_launch(const SharedParams& p, int n_slices, hipStream_t st)
 }
 
 template <int ROLE>
-static int ss_dispatch(const SharedParams& p, int n_slices, hipStream_t st)
+static int ss_dispatch(const SharedParams& p, int n_slices, hipStream_t st, const SharedHits* h = nullptr)
 {
-    if (p.d <= 32) return ss_launch<32, ROLE>(p, n_slices, st);
-    if (p.d <= 64) return ss_launch<64, ROLE>(p, n_slices, st);
-    return ss_launch<128, ROLE>(p, n_slices, st);
+    if (p.d <= 32) return ss_launch<32, ROLE>(p, n_slices, st, h);
+    if (p.d <= 64) return ss_launch<64, ROLE>(p, n_slices, st, h);
+    return ss_launch<128, ROLE>(p, n_slices, st, h);
 }
 
 
@@ -412,6 +283,36 @@ extern "C" int trec_softmax_shared_positives(const int64_t* indptr, const int32_
     return trec_check_launch("trec_softmax_shared_positives");
 }
 
+// the launches of trec_softmax_shared_grads and trec_softmax_shared_hits_grads (h: accidental hits removed), arguments checked
+static int ss_grads(const float* U, const float* Vs, const float* user_bias, const float* sample_bias, const float* sample_c,
+                    const float* M, const float* tK, int64_t n_users, int32_t n_sampled, int32_t d, float inv_temperature,
+                    int32_t n_slices, float* workspace, float* dU, float* dVs, float* d_sample_bias, const SharedHits* h, hipStream_t st)
+{
+    SharedParams p = {};
+    p.d = d; p.inv_t = inv_temperature; p.cs = sample_c; p.M = M; p.tK = tK;
+    // dU: users resident, every sample streamed
+    p.R = U; p.T = Vs; p.n_res = n_users; p.n_str = n_sampled; p.r_bias = user_bias; p.t_bias = sample_bias;
+    p.slice_len = ceil_div64(n_sampled, 32) * 32;
+    p.n_rblocks = (int)ceil_div64(n_users, 128);
+    p.out = dU;
+    int rc = ss_dispatch<SS_DU>(p, 1, st, h);
+    if (rc != TREC_OK) return rc;
+    // dV, d b_s: samples resident, the users streamed in slices
+    const int64_t sd = (int64_t)n_sampled * d;
+    p.R = Vs; p.T = U; p.n_res = n_sampled; p.n_str = n_users; p.r_bias = sample_bias; p.t_bias = user_bias;
+    p.slice_len = ceil_div64(ceil_div64(n_users, 32), n_slices) * 32;
+    p.n_rblocks = (int)ceil_div64(n_sampled, 128);
+    p.out = n_slices == 1 ? dVs : workspace;
+    p.out_sum = d_sample_bias ? (n_slices == 1 ? d_sample_bias : workspace + (int64_t)n_slices * sd) : nullptr;
+    rc = ss_dispatch<SS_DV>(p, n_slices, st, h);
+    if (rc != TREC_OK || n_slices == 1) return rc;
+    hipLaunchKernelGGL(shared_reduce_slices_kernel, dim3((unsigned)ceil_div64(sd, 256)), dim3(256), 0, st, workspace, sd, n_slices, dVs);
+    if (d_sample_bias)
+        hipLaunchKernelGGL(shared_reduce_slices_kernel, dim3((unsigned)ceil_div64(n_sampled, 256)), dim3(256), 0, st,
+                           workspace + (int64_t)n_slices * sd, (int64_t)n_sampled, n_slices, d_sample_bias);
+    return trec_check_launch("trec_softmax_shared_grads");
+}
+
 extern "C" int trec_softmax_shared_grads(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
                                          const float* sample_c, const float* M, const float* tK, int64_t n_users, int32_t n_sampled,
                                          int32_t d, float inv_temperature, int32_t n_slices, float* workspace, float* dU, float* dVs,
@@ -425,30 +326,8 @@ extern "C" int trec_softmax_shared_grads(const float* U, const float* Vs, const 
     TREC_REQUIRE(n_slices == trec_softmax_shared_slices(n_users, n_sampled, d),
                  "trec_softmax_shared_grads: n_slices must be trec_softmax_shared_slices' answer");
     TREC_REQUIRE(n_slices == 1 || workspace, "trec_softmax_shared_grads: more than one slice needs the workspace");
-    hipStream_t st = (hipStream_t)stream;
-    SharedParams p = {};
-    p.d = d; p.inv_t = inv_temperature; p.cs = sample_c; p.M = M; p.tK = tK;
-    // dU: users resident, every sample streamed
-    p.R = U; p.T = Vs; p.n_res = n_users; p.n_str = n_sampled; p.r_bias = user_bias; p.t_bias = sample_bias;
-    p.slice_len = ceil_div64(n_sampled, 32) * 32;
-    p.n_rblocks = (int)ceil_div64(n_users, 128);
-    p.out = dU;
-    int rc = ss_dispatch<SS_DU>(p, 1, st);
-    if (rc != TREC_OK) return rc;
-    // dV, d b_s: samples resident, the users streamed in slices
-    const int64_t sd = (int64_t)n_sampled * d;
-    p.R = Vs; p.T = U; p.n_res = n_sampled; p.n_str = n_users; p.r_bias = sample_bias; p.t_bias = user_bias;
-    p.slice_len = ceil_div64(ceil_div64(n_users, 32), n_slices) * 32;
-    p.n_rblocks = (int)ceil_div64(n_sampled, 128);
-    p.out = n_slices == 1 ? dVs : workspace;
-    p.out_sum = d_sample_bias ? (n_slices == 1 ? d_sample_bias : workspace + (int64_t)n_slices * sd) : nullptr;
-    rc = ss_dispatch<SS_DV>(p, n_slices, st);
-    if (rc != TREC_OK || n_slices == 1) return rc;
-    hipLaunchKernelGGL(shared_reduce_slices_kernel, dim3((unsigned)ceil_div64(sd, 256)), dim3(256), 0, st, workspace, sd, n_slices, dVs);
-    if (d_sample_bias)
-        hipLaunchKernelGGL(shared_reduce_slices_kernel, dim3((unsigned)ceil_div64(n_sampled, 256)), dim3(256), 0, st,
-                           workspace + (int64_t)n_slices * sd, (int64_t)n_sampled, n_slices, d_sample_bias);
-    return trec_check_launch("trec_softmax_shared_grads");
+    return ss_grads(U, Vs, user_bias, sample_bias, sample_c, M, tK, n_users, n_sampled, d, inv_temperature, n_slices, workspace, dU, dVs,
+                    d_sample_bias, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int64_t* order, const float* dVs, const float* d_sample_bias,
@@ -459,6 +338,66 @@ extern "C" int trec_softmax_shared_scatter(const int32_t* sorted_ids, const int6
     hipLaunchKernelGGL(shared_scatter_kernel, dim3((unsigned)ceil_div64((int64_t)n_sampled * (d + 1), 256)), dim3(256), 0,
                        (hipStream_t)stream, sorted_ids, order, dVs, d_sample_bias, n_sampled, d, n_items, dV, d_item_bias);
     return trec_check_launch("trec_softmax_shared_scatter");
+}
+
+// ---- accidental hits removed: the columns (Vs, sample_bias, sample_c) in SORTED id order (include/tensorrec_hip.h)
+extern "C" int trec_softmax_shared_hit_ranges(const int64_t* indptr, const int32_t* x_item, const int32_t* pos_slot,
+                                              const int32_t* sorted_ids, int64_t n_users, int32_t n_sampled, int32_t* hit_rng,
+                                              int32_t* hit_cnt, void* stream)
+{
+    TREC_REQUIRE(indptr && x_item && pos_slot && sorted_ids && hit_rng && hit_cnt, "trec_softmax_shared_hit_ranges: null pointer");
+    TREC_REQUIRE(n_sampled >= 1, "trec_softmax_shared_hit_ranges: n_sampled must be >= 1");
+    TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_shared_hit_ranges: n_users must fit int32");
+    if (n_users == 0) return TREC_OK;
+    hipLaunchKernelGGL(shared_hit_ranges_kernel, dim3((unsigned)ceil_div64(n_users, 256)), dim3(256), 0, (hipStream_t)stream, indptr,
+                       x_item, pos_slot, sorted_ids, n_users, n_sampled, hit_rng, hit_cnt);
+    return trec_check_launch("trec_softmax_shared_hit_ranges");
+}
+
+extern "C" int trec_softmax_shared_hits_stats(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                                              const float* sample_c, const int64_t* indptr, const int32_t* hit_rng,
+                                              const int32_t* hit_cnt, int64_t n_users, int32_t n_sampled, int32_t d,
+                                              float inv_temperature, float* M, float* Z, void* stream)
+{
+    TREC_REQUIRE(U && Vs && M && Z && indptr && hit_rng && hit_cnt, "trec_softmax_shared_hits_stats: null pointer");
+    TREC_REQUIRE(n_sampled >= 1, "trec_softmax_shared_hits_stats: n_sampled must be >= 1");
+    TREC_REQUIRE(ss_shape_ok(n_sampled, d), "trec_softmax_shared_hits_stats: need d % 4 == 0 and 4 <= d <= 128");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_shared_hits_stats: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_shared_hits_stats: n_users must fit int32");
+    if (n_users == 0) return TREC_OK;
+    SharedParams p = {};
+    p.R = U; p.T = Vs; p.n_res = n_users; p.n_str = n_sampled; p.d = d;
+    p.r_bias = user_bias; p.t_bias = sample_bias; p.cs = sample_c; p.inv_t = inv_temperature;
+    p.slice_len = ceil_div64(n_sampled, 32) * 32;
+    p.n_rblocks = (int)ceil_div64(n_users, 128);
+    p.out_M = M; p.out_Z = Z;
+    SharedHits h = {};
+    h.indptr = indptr; h.hit_rng = hit_rng; h.hit_cnt = hit_cnt;
+    return ss_dispatch<SS_STATS>(p, 1, (hipStream_t)stream, &h);
+}
+
+extern "C" int trec_softmax_shared_hits_grads(const float* U, const float* Vs, const float* user_bias, const float* sample_bias,
+                                              const float* sample_c, const float* M, const float* tK, const int64_t* indptr,
+                                              const int32_t* hit_rng, const int32_t* hit_cnt, const int32_t* sorted_ids,
+                                              const int64_t* indptr_tp, const int32_t* users_tp, int64_t n_items, int64_t n_users,
+                                              int32_t n_sampled, int32_t d, float inv_temperature, int32_t n_slices, float* workspace,
+                                              float* dU, float* dVs, float* d_sample_bias, void* stream)
+{
+    TREC_REQUIRE(U && Vs && M && tK && dU && dVs, "trec_softmax_shared_hits_grads: null pointer");
+    TREC_REQUIRE(indptr && hit_rng && hit_cnt && sorted_ids && indptr_tp && users_tp, "trec_softmax_shared_hits_grads: null pointer");
+    TREC_REQUIRE(n_sampled >= 1 && n_items >= 1, "trec_softmax_shared_hits_grads: n_sampled and n_items must be >= 1");
+    TREC_REQUIRE(ss_shape_ok(n_sampled, d), "trec_softmax_shared_hits_grads: need d % 4 == 0 and 4 <= d <= 128");
+    TREC_REQUIRE(temperature_ok(inv_temperature), "trec_softmax_shared_hits_grads: inv_temperature must be finite and > 0");
+    TREC_REQUIRE(n_users >= 0 && n_users < ((int64_t)1 << 31), "trec_softmax_shared_hits_grads: n_users must fit int32");
+    if (n_users == 0) return TREC_OK;
+    TREC_REQUIRE(n_slices == trec_softmax_shared_slices(n_users, n_sampled, d),
+                 "trec_softmax_shared_hits_grads: n_slices must be trec_softmax_shared_slices' answer");
+    TREC_REQUIRE(n_slices == 1 || workspace, "trec_softmax_shared_hits_grads: more than one slice needs the workspace");
+    SharedHits h = {};
+    h.indptr = indptr; h.hit_rng = hit_rng; h.hit_cnt = hit_cnt;
+    h.sorted_ids = sorted_ids; h.indptr_tp = indptr_tp; h.users_tp = users_tp; h.n_items = n_items;
+    return ss_grads(U, Vs, user_bias, sample_bias, sample_c, M, tK, n_users, n_sampled, d, inv_temperature, n_slices, workspace, dU, dVs,
+                    d_sample_bias, &h, (hipStream_t)stream);
 }
 
 // the positives of the full softmax (full_positives_kernel): pred_serial = K3's scores of the interactions, (M, Z) = _stats' answer

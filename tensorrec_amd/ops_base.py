@@ -901,17 +901,19 @@ GROUP_BINNED_MIN_PAIRS = int(_os.environ.get("TREC_BINNED_MIN_PAIRS", 1 << 22)) 
 def step_switch(name):
     """Is the tuning switch ``name`` of the training step on?  (All default on; "softmax_shared" defaults to SOFTMAX_SHARED_DEFAULT,
     "softmax_full" to SOFTMAX_FULL_DEFAULT, "warp_fused" to WARP_FUSED_DEFAULT, "softmax_tiled" to SOFTMAX_TILED_DEFAULT, "bpr_fused" to
-    BPR_FUSED_DEFAULT.)"""
+    BPR_FUSED_DEFAULT, "softmax_shared_hits" to SOFTMAX_SHARED_HITS_DEFAULT.)"""
     default = {"softmax_shared": SOFTMAX_SHARED_DEFAULT, "softmax_full": SOFTMAX_FULL_DEFAULT, "warp_fused": WARP_FUSED_DEFAULT,
-               "softmax_tiled": SOFTMAX_TILED_DEFAULT, "bpr_fused": BPR_FUSED_DEFAULT}.get(name, 1)
+               "softmax_tiled": SOFTMAX_TILED_DEFAULT, "bpr_fused": BPR_FUSED_DEFAULT,
+               "softmax_shared_hits": SOFTMAX_SHARED_HITS_DEFAULT}.get(name, 1)
     return N.load().trec_get_tuning(name.encode(), default) != 0
 
 
 def step_covers(kernel, n_sampled, max_row_nnz, d):
-    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_tiled", "warp_fused", "bpr_fused", "softmax_shared") cover this shape?  The ONE
+    """Does the one-pass step ``kernel`` ("wmrb_fused", "wmrb_tiled", "softmax_fused", "softmax_tiled", "warp_fused", "bpr_fused", "softmax_shared", "softmax_shared_hits") cover this shape?  The ONE
     statement of the coverage: the native library's shape query (host arithmetic, needs no GPU); step_plan.kernel and the
     ``*_supported`` functions below both ask here."""
-    if kernel == "softmax_shared":         # (the interactions do not restrict it: the positives are O(P) work on K3's scores)
+    if kernel in ("softmax_shared", "softmax_shared_hits"):     # (the interactions do not restrict it: the positives are O(P) work on
+                                                                # K3's scores; the masked instantiations cover what the plain ones do)
         return bool(N.query("trec_softmax_shared_supported", int(n_sampled), int(d)))
     return N.query("trec_%s_lds_bytes" % kernel, int(n_sampled), int(max_row_nnz), int(d)) >= 0
 
@@ -1227,6 +1229,81 @@ def softmax_shared_step(user_in, item_in, user_bias, item_bias, interactions, sa
     sorted_ids, order = torch.sort(samples, stable=True)
     N.call("trec_softmax_shared_scatter", N.ptr(sorted_ids.contiguous()), N.ptr(order.contiguous()), N.ptr(d_vs), N.ptr(d_bs), S, d,
            n_items, N.ptr(d_v), N.ptr(d_ib))
+    return loss, pred, d_u, d_v, d_ub, d_ib
+
+
+SOFTMAX_SHARED_HITS_DEFAULT = 0  # tuning "softmax_shared_hits" when nobody set it: the route is opt-in (docs/sampled_losses.md, "Accidental hits on the shared route")
+
+
+def softmax_shared_hits_supported(n_sampled, interactions, d):
+    """Can the shared-negatives MFMA step with accidental hits removed run this shape, and is tuning ``softmax_shared_hits`` on (it
+    defaults to off)?"""
+    return _step_supported("softmax_shared_hits", n_sampled, interactions, d)
+
+
+def softmax_shared_hits_step(user_in, item_in, user_bias, item_bias, interactions, samples, temperature, sample_log_q=None,
+                             log_q_correction=False):
+    """softmax_shared_step with ACCIDENTAL HITS REMOVED: the step softmax_fused_step(remove_accidental_hits=True) would make of the
+    [n_users, S] table that repeats ``samples`` -- a column whose id is the item of one of the user's interactions with pos_slot >= 0
+    leaves that user's M and Z and has a coefficient of exactly 0; c_s keeps the full S.  Returns (loss [P+], pred_serial [P],
+    d user_in, d item_in, d user_bias, d item_bias).  The columns are worked in SORTED id order (the sort the scatter needs anyway):
+    a user's hits are then ascending column ranges (trec_softmax_shared_hit_ranges: nnz pairs, n_users counts) and the users a
+    column is masked for are a row of interactions.transposed_positive().  Nothing of size [U, S] exists, every workspace is sized
+    from (nnz, n_users, S) alone, there are no float atomics and nothing is read on the host."""
+    temperature = _checked_temperature(temperature)
+    u, v, ub, ib = _step_operands(user_in, item_in, user_bias, item_bias)
+    n_users, n_items = interactions.shape
+    if samples.dim() != 1 or samples.numel() < 1:
+        raise ValueError("samples must be a vector of n_sampled >= 1 item ids")
+    S, d, dev, nnz = int(samples.numel()), int(u.shape[1]), u.device, interactions.nnz
+    if not step_covers("softmax_shared_hits", S, 0, d):
+        raise ValueError("softmax_shared_hits_step covers d %% 4 == 0, 4 <= d <= %d; got d = %d" % (SOFTMAX_SHARED_MAX_D, d))
+    inv_t = 1.0 / temperature
+    sorted_ids, _ = torch.sort(samples.to(torch.int32).contiguous(), stable=True)
+    ids = sorted_ids.long()
+    vs = v.index_select(0, ids)
+    bs = ib.index_select(0, ids) if ib is not None else None
+    cs = None
+    if log_q_correction:                                          # (the same floats as softmax_shared_step's, in sorted order)
+        if sample_log_q is not None:
+            cs = -(_checked_log_q(sample_log_q, n_items).index_select(0, ids) + _f32r(math.log(S)))
+        else:
+            cs = torch.full((S,), -_f32r(_f32r(math.log(S)) + _f32r(-math.log(n_items))), dtype=torch.float32, device=dev)
+    hit_rng = torch.empty((max(nnz, 1), 2), dtype=torch.int32, device=dev)
+    hit_cnt = torch.empty((n_users,), dtype=torch.int32, device=dev)
+    indptr_tp, users_tp = interactions.transposed_positive()
+    N.call("trec_softmax_shared_hit_ranges", N.ptr(interactions.indptr), N.ptr(interactions.x_item32), N.ptr(interactions.pos_slot),
+           N.ptr(sorted_ids), n_users, S, N.ptr(hit_rng), N.ptr(hit_cnt))
+    loss = torch.empty((interactions.n_positive,), dtype=torch.float32, device=dev)
+    pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    d_pred = torch.empty((nnz,), dtype=torch.float32, device=dev)
+    stat_m = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    stat_z = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    t_k = torch.empty((n_users,), dtype=torch.float32, device=dev)
+    d_ub = torch.empty((n_users,), dtype=torch.float32, device=dev) if ub is not None else None
+    with _timed("softmax_shared_hits_stats"):
+        N.call("trec_softmax_shared_hits_stats", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), N.ptr(interactions.indptr),
+               N.ptr(hit_rng), N.ptr(hit_cnt), n_users, S, d, inv_t, N.ptr(stat_m), N.ptr(stat_z))
+    if nnz:
+        N.call("trec_pair_score_fwd", N.ptr(u), N.ptr(v), N.ptr(interactions.x_user32), N.ptr(interactions.x_item32), nnz, 0, d,
+               MODE_DOT, N.ptr(ub), N.ptr(ib), N.ptr(pred), None)
+    # (M = -inf, Z = 0 of a user whose samples are all hits: the unchanged kernel gives loss 0, d y_p -0, tK 0 -- m = w_p, b = 0, D = 1)
+    N.call("trec_softmax_shared_positives", N.ptr(interactions.indptr), N.ptr(interactions.pos_slot), N.ptr(pred), N.ptr(stat_m),
+           N.ptr(stat_z), n_users, inv_t, N.ptr(loss), N.ptr(d_pred), N.ptr(t_k), N.ptr(d_ub))
+    d_u = _gather_over_users(interactions, d_pred, v) if nnz else torch.zeros_like(u)
+    d_ib = torch.zeros((n_items,), dtype=torch.float32, device=dev) if ib is not None else None
+    d_v = _gather_over_items(interactions, d_pred, u, d_ib) if nnz else torch.zeros_like(v)
+    d_vs = torch.empty((S, d), dtype=torch.float32, device=dev)
+    d_bs = torch.empty((S,), dtype=torch.float32, device=dev) if ib is not None else None
+    n_slices = int(N.query("trec_softmax_shared_slices", n_users, S, d))
+    ws = torch.empty((n_slices * S * (d + 1),), dtype=torch.float32, device=dev) if n_slices > 1 else None
+    with _timed("softmax_shared_hits_grads"):
+        N.call("trec_softmax_shared_hits_grads", N.ptr(u), N.ptr(vs), N.ptr(ub), N.ptr(bs), N.ptr(cs), N.ptr(stat_m), N.ptr(t_k),
+               N.ptr(interactions.indptr), N.ptr(hit_rng), N.ptr(hit_cnt), N.ptr(sorted_ids), N.ptr(indptr_tp), N.ptr(users_tp),
+               n_items, n_users, S, d, inv_t, n_slices, N.ptr(ws), N.ptr(d_u), N.ptr(d_vs), N.ptr(d_bs))
+    order = torch.arange(S, dtype=torch.int64, device=dev)        # the rows of d_vs ARE in sorted order: runs of equal ids fold in place
+    N.call("trec_softmax_shared_scatter", N.ptr(sorted_ids), N.ptr(order), N.ptr(d_vs), N.ptr(d_bs), S, d, n_items, N.ptr(d_v),
+           N.ptr(d_ib))
     return loss, pred, d_u, d_v, d_ub, d_ib
 
 

@@ -127,6 +127,7 @@ class Interactions(object):
         self._host = m
         self._balanced_weight = None
         self._t = None
+        self._tp = None
 
     def transposed(self):
         """(indptr_t int64 [n_items+1], users_t int32 [nnz], perm_t int32 [nnz]): the interactions grouped by item;
@@ -144,6 +145,23 @@ class Interactions(object):
             self._t = (_dev(indptr_t, self.device), _dev(t.indices.astype(np.int32), self.device),
                        _dev((t.data - 1).astype(np.int32), self.device))
         return self._t
+
+    def transposed_positive(self):
+        """(indptr_tp int64 [n_items+1], users_tp int32 [max(n_positive, 1)]): ``transposed()`` restricted to the interactions with
+        ``pos_slot >= 0`` (value > 0) -- per item the users, ascending, that have it as a positive.  Static, built once on the host:
+        the shared-negatives step with accidental hits removed (ops.softmax_shared_hits_step) finds in it the users a sampled item
+        is masked for.  (One padding entry when there is no positive, so the array is never empty.)"""
+        if self._tp is None:
+            m = self._host
+            keep = m.data.astype(np.float32) > 0.0
+            rows = np.repeat(np.arange(m.shape[0], dtype=np.int64), np.diff(m.indptr))[keep]
+            cols = m.indices[keep].astype(np.int64)
+            order = np.lexsort((rows, cols))                   # by item, users ascending within an item
+            indptr_tp = np.zeros(self.shape[1] + 1, np.int64)
+            np.cumsum(np.bincount(cols, minlength=self.shape[1]), out=indptr_tp[1:])
+            users_tp = rows[order].astype(np.int32) if keep.any() else np.zeros(1, np.int32)
+            self._tp = (_dev(indptr_tp, self.device), _dev(users_tp, self.device))
+        return self._tp
 
     @property
     def indices(self):

@@ -137,6 +137,26 @@ def softmax_tiled_kernel(loss, engine, engine_mode, multi, same_width, n_sampled
     return "softmax_tiled" if on else None
 
 
+def softmax_shared_hits_kernel(loss, engine, engine_mode, multi, same_width, n_sampled, d, shared_negatives, remove_accidental_hits,
+                               switch=None):
+    """The one-pass kernel of a sampled-softmax step with ONE shared row of samples AND accidental hits removed, which ``kernel``
+    leaves to the expanded generic step -- "softmax_shared_hits" (csrc/softmax_shared.hip's masked instantiations,
+    ops.softmax_shared_hits_step) -- or None: the generic step.  ``loss``: loss_kind's answer ("sampled_softmax": the exact class);
+    a built-in prediction graph in MODE_DOT (cosine counts as dot: the step is fed the normalised operands), one taste, both
+    representations 2-D and equally wide (``d`` that width), ``n_sampled`` given, shared negatives and hits removed -- both --, then
+    the shape must be covered (ops.step_covers) and BOTH switches on: tuning "softmax_shared" (the MFMA route as such, as the
+    library holds it) and ``switch``: tuning "softmax_shared_hits", None reads the library's (ops.SOFTMAX_SHARED_HITS_DEFAULT: off).
+    TensorRec._train_step asks only where ``kernel`` said None."""
+    if loss != "sampled_softmax" or not engine or engine_mode != ops.MODE_DOT or multi or not same_width or n_sampled is None:
+        return None
+    if not shared_negatives or not remove_accidental_hits:
+        return None
+    if not ops.step_covers("softmax_shared_hits", n_sampled, 0, d):
+        return None
+    on = ops.step_switch("softmax_shared_hits") if switch is None else switch
+    return "softmax_shared_hits" if on and ops.step_switch("softmax_shared") else None
+
+
 def graph_eligible(hip_graphs, dp, capturing, deterministic, shared_negatives, loss_capturable, engine_graph, n_graphs, nnz, n_users,
                    n_items, n_sampled, dense_loss, scored_sampler=False):
     """May this batch's step be captured in a HIP graph and replayed?  Single process, no gradient capture, no deterministic grouping;

@@ -437,7 +437,8 @@ class TensorRec(object):
                                       # "softmax_shared", "softmax_full" (step_plan.dense_kernel), "warp_fused" (step_plan.warp_kernel:
                                       # only with tuning warp_fused = 1), "softmax_tiled" (step_plan.softmax_tiled_kernel: only
                                       # with tuning softmax_tiled = 1), "bpr_fused" (step_plan.bpr_kernel: only with tuning
-                                      # bpr_fused = 1);
+                                      # bpr_fused = 1), "softmax_shared_hits" (step_plan.softmax_shared_hits_kernel: only with
+                                      # tuning softmax_shared_hits = 1);
                                       # None: the generic step (scores -> loss -> autograd).  Set on every eager step and on capture
         self.last_step_form = None    # how the last training step ran: "coop" (one cooperative kernel), "graph" (HIP-graph replay), "eager"
         self._capture = None          # tests set this to a dict to receive the last step's loss and raw gradients
@@ -913,6 +914,11 @@ class TensorRec(object):
                 kernel = step_plan.softmax_tiled_kernel(step_plan.loss_kind(loss_graph), engine, getattr(graph, 'engine_mode', None),
                                                         multi, same_width, n_sampled_items, inter.max_row_nnz,
                                                         int(item_repr.shape[-1]), shared)
+            if kernel is None:          # one shared row with accidental hits removed: the masked MFMA step, opt-in as well
+                kernel = step_plan.softmax_shared_hits_kernel(step_plan.loss_kind(loss_graph), engine,
+                                                              getattr(graph, 'engine_mode', None), multi, same_width, n_sampled_items,
+                                                              int(item_repr.shape[-1]), shared,
+                                                              getattr(loss_graph, 'remove_accidental_hits', False))
             if kernel is not None:
                 return self._one_pass_step(kernel, inter, u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
                                            n_sampled_items, want_stats, samples, apply)
@@ -1034,6 +1040,8 @@ class TensorRec(object):
                 out = ops.softmax_tiled_step(*operands, samples, loss_graph.temperature,
                                              remove_accidental_hits=loss_graph.remove_accidental_hits,
                                              mode=self.prediction_graph_factory.engine_mode, **options)
+            elif kernel == "softmax_shared_hits":      # the one row every user shares, each user's own positives masked out of it
+                out = ops.softmax_shared_hits_step(*operands, samples[0], loss_graph.temperature, **options)
             else:                          # "softmax_shared": the one row every user shares
                 out = ops.softmax_shared_step(*operands, samples[0], loss_graph.temperature, **options)
         return self._finish_fused_step(out[0], out[1], out[2:], u_in, i_in, user_bias, item_bias, weights, learning_rate, alpha,
