@@ -35,27 +35,56 @@ constexpr int NWQ = 4;          // waves per workgroup sharing one item tile str
 // i8 16x16x64 4.05 Pop/s (bf16 32x32x16: 1.80 PF).  The 16x16x64 form does the same work per operand byte (a 16-item x 64-k
 // fragment, one ds_read_b128, feeds one MFMA per 16-user block of the wave) and needs half the accumulator
 // registers.  Lane = (k-group g = lane >> 4 of the operands | row-group g of the result, user /
-// item row lane & 15): the maxima of the four row-groups are combined by two shuffles at a superblock end, after which
-// row-group g owns NUB / 4 of the user blocks (their table stores, bound constants and top-k register lists: NUB / 4 x TK
-// registers, not NUB x TK).
+// item row lane & 15): the maxima of the four row-groups are combined at a superblock end by a reduce-scatter in registers
+// (NUB / 2 v_permlane32_swap + NUB / 4 v_permlane16_swap, one v_max each; no LDS), after which row-group g owns NUB / 4 of the
+// user blocks (their table stores, bound constants and top-k register lists: NUB / 4 x TK registers, not NUB x TK).
 // NUB: 16-user blocks per wave.  12 (192 users: a third fewer LDS reads and tile streams per flop, 78.8 against 81.9 ms at
 // 1M x 1M with the 10-slot lists, profiles/r02_power_trace_i8.txt) unless the 16-slot lists need the registers: then 8.
 // TK > 0: the kernel also keeps, per user, the TK largest LOWER bounds M - e(u, s) of the superblocks of its chunk (sorted
 // registers, one insertion per superblock end) and writes them to chunk_top: the k-th largest over the chunks' lists is
 // tau8 -- no pass over the 7.8 GB table for it.
-// A step's LDS operand prefetch (for step s + 2) is issued AFTER the step's MFMAs: the compiler closes every block start with
-// s_waitcnt lgkmcnt(0) -- a full drain, although the operands the MFMAs need were read two steps earlier -- so a prefetch
-// issued right in front of it is waited for at its full LDS latency, once per 24 MFMAs; issued after the MFMAs, the next
-// drain finds it a whole group of max3 old.
+// A wave keeps the matrix pipe busy on its own.  The two v_max3_i32 of a block's acc[ub] stand directly in front of the MFMA of
+// the NEXT block that overwrites acc[ub] (one MFMA holds vector issue for 8 of its 16 cycles; two max3 fill the other 8), the
+// last block of a tile is flushed behind the tile; the LDS reads of step s + 1 (item fragment, and the next block's bias quad)
+// follow the FIRST MFMA of step s, so the s_waitcnt lgkmcnt(0) in front of step s + 1 finds them NUB - 1 MFMAs old.  Every
+// MFMA is followed by sched_barrier(0): the emitted tile body is this order exactly (longest run of vector instructions
+// between two MFMAs of a tile: 2; 24 before).  Two operand quads in turn, not three: the registers of all K = 128 forms are what
+// they were or fewer (256 VGPRs, 6 dwords spilled outside the loop at <128, true, 10, 12>); the K = 64 bias forms take 2 more (a
+// second bias quad: their only k-step reads one while the next is fetched), occupancy unchanged.
+// Measured at 1M x 1M, same box, alternating (profiles/i8_stage_attribution.json): 77.4 / 77.8 ms before, 77.0 / 77.1 with the
+// tile body alone, 75.4 / 75.6 with the register combine as well; on all-zero operands (2.39 GHz, below the cap: cycles, not
+// clock) 63.5 / 63.6 -> 62.4 / 62.5 -> 60.3 / 60.4.  Under the cap the clock gives about half of the cycles back (2005 -> 1960 MHz).
+// Where wave 0 of a workgroup spends its life (s_memtime stamps, make diag): tile bodies 73 %, tile boundaries (wait + barrier +
+// DMA issue, ~1,200 clocks per tile) 18 %, superblock ends (~2,400 clocks each, the stores' acknowledgement included: the
+// waits on vmcnt in front of the next tile count stores too) 9 % -- 77 / 16 / 7 % before.
 // Tried and measured slower, at 1M x 1M on one box (docs/history/DESIGN_rounds_1_to_5.md), and deleted:
 //   the same stage on v_mfma_i32_32x32x32_i8 (the first form of this kernel): 91-94 ms against 78.8 ms;
 //   8 waves per workgroup (one workgroup per CU), 256-row tiles, the other users-per-wave count: slower each;
 //   the prefetch before the step's MFMAs 78.1 ms, in the middle of them 77.2 ms, after them with the block's max3 pinned
-//   between the MFMAs by sched_group_barrier 75.5 ms -- against 75.7 ms as shipped (two waves per SIMD already cover each
-//   other's max3 phase).
+//   between the MFMAs by sched_group_barrier 75.5 ms -- against 75.7 ms with the max3 in one run behind the block (that trial
+//   moved the maxima alone and kept the full drain per block, the late prefetch and the LDS combine);
+//   three operand quads with the prefetch two steps ahead: the same emitted order at 4 VGPRs more per form (the 16-slot K = 64
+//   form falls from three to two waves per SIMD) -- not measured, the two-quad form already hides the read.
+// Not done: branch-free table stores and a scalar row base per superblock -- the emitted superblock end already forms the row
+// base in scalars (one v_lshl_add_u64 and immediate offsets per store group) and its three exec-mask branches are never taken.
+#ifdef TREC_I8_DIAG
+// diagnostics build only (make diag; scripts/i8_stage_attribution.py): where wave 0 of every workgroup of the LAST launch spends
+// its life, in shader clocks (s_memtime) -- {entry -> first tile body, sum of the tile bodies, sum of the tile boundaries (the wait
+// and barrier behind a tile + the DMA issue of the next), sum of the superblock ends, whole life, tiles | superblocks << 32}.
+// Stamps stand around whole tiles and superblock ends, never inside a tile, and go out as plain stores at the exit; the shipped
+// kernel has none of it.
+constexpr int I8_DIAG_WGS = 1 << 16;
+constexpr int I8_DIAG_WORDS = 6;
+__device__ unsigned long long g_i8_clk[(size_t)I8_DIAG_WGS * I8_DIAG_WORDS];
+#define I8_DIAG(...) __VA_ARGS__
+#else
+#define I8_DIAG(...)
+#endif
+
 template <int KT, bool BIAS, int TK, int NUB>
 __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(ScoreParams p)
 {
+    I8_DIAG(const unsigned long long dg_t0 = __builtin_amdgcn_s_memtime(); unsigned long long dg_body = 0, dg_bound = 0, dg_sbend = 0; unsigned dg_nsb = 0;)
     constexpr int NT = NWQ * 64;              // threads per workgroup
     constexpr int OW = NUB / 4;              // user blocks a row-group owns at superblock ends
     static_assert(NUB % 4 == 0, "user blocks per wave must split over the four row-groups");
@@ -165,38 +194,48 @@ __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(Score
         constexpr int buf = decltype(bufc)::value;
         const char* tb = smem + buf * TILE_BYTES;
         const int* sd = side + buf * BNQ + 4 * g;                // the block's integer biases of result rows 4 g .. 4 g + 3
-        v4i32 tf[3];
-        v4i32 c0 = {0, 0, 0, 0};
-        if (BIAS) c0 = *(const v4i32*)sd;
+        v4i32 tf[2];
+        // the bias quad of block blk: one register quad at KS > 1 (the last k-step of a block does not read it, so the next
+        // block's quad is fetched there), two in turn at KS == 1 (the only step reads one while the next is fetched)
+        constexpr int NC0 = KS == 1 ? 2 : 1;
+        v4i32 c0[NC0];
+        c0[0] = (v4i32){0, 0, 0, 0};
+        if (NC0 > 1) c0[NC0 - 1] = (v4i32){0, 0, 0, 0};
+        if (BIAS) c0[0] = *(const v4i32*)sd;
         tf[0] = *(const v4i32*)(tb + koff[0]);
-        tf[1] = *(const v4i32*)(tb + (KS > 1 ? koff[1 % KS] : 16 * RB + koff[0]));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
             const int blk = s / KS, ks = s % KS;
-            if (ks == 0) {
 #pragma unroll
-                for (int ub = 0; ub < NUB; ++ub)
-                    acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 3], rfq[ub][0], c0, 0, 0, 0);
+            for (int ub = 0; ub < NUB; ++ub) {
+                if (ks == 0) {
+                    // the two max3 of the previous block's acc[ub], in the issue gap in front of the MFMA that overwrites it
+                    if (blk > 0) {
+                        bm[ub] = max(max(bm[ub], acc[ub][0]), acc[ub][1]);
+                        bm[ub] = max(max(bm[ub], acc[ub][2]), acc[ub][3]);
+                    }
+                    acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 2], rfq[ub][0], c0[blk % NC0], 0, 0, 0);
+                } else {
+                    acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 2], rfq[ub][ks], acc[ub], 0, 0, 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
-                if (BIAS && blk + 1 < NBLK) c0 = *(const v4i32*)(sd + 16 * (blk + 1));     // lands under this block's MFMAs
-            } else {
-#pragma unroll
-                for (int ub = 0; ub < NUB; ++ub)
-                    acc[ub] = __builtin_amdgcn_mfma_i32_16x16x64_i8(tf[s % 3], rfq[ub][ks], acc[ub], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // the operand prefetch for step s + 2, behind this step's MFMAs (see the header)
-            if (s + 2 < NSTEP) tf[(s + 2) % 3] = *(const v4i32*)(tb + ((s + 2) / KS) * 16 * RB + koff[(s + 2) % KS]);
-            if (ks == KS - 1) {
-#pragma unroll
-                for (int ub = 0; ub < NUB; ++ub) {
-                    bm[ub] = max(max(bm[ub], acc[ub][0]), acc[ub][1]);
-                    bm[ub] = max(max(bm[ub], acc[ub][2]), acc[ub][3]);
+                if (ub == 0) {
+                    // the LDS reads for step s + 1 and for the next block's bias, behind the step's first MFMA: the wait that
+                    // retires them finds them NUB - 1 MFMAs old (see the header)
+                    if (s + 1 < NSTEP) tf[(s + 1) % 2] = *(const v4i32*)(tb + ((s + 1) / KS) * 16 * RB + koff[(s + 1) % KS]);
+                    if (BIAS && ks == KS - 1 && blk + 1 < NBLK) c0[(blk + 1) % NC0] = *(const v4i32*)(sd + 16 * (blk + 1));
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            __builtin_amdgcn_sched_barrier(0);
         }
+        // the last block's maxima: nothing overwrites acc[] behind it in this tile
+#pragma unroll
+        for (int ub = 0; ub < NUB; ++ub) {
+            bm[ub] = max(max(bm[ub], acc[ub][0]), acc[ub][1]);
+            bm[ub] = max(max(bm[ub], acc[ub][2]), acc[ub][3]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
     };
 
     stage_issue(0, 0);
@@ -206,13 +245,16 @@ __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(Score
     const float a_user = p.wg_scale ? p.wg_scale[rblock] : p.scales[0];      // the scale of this workgroup's users
     const int64_t sb0 = t_begin / ((int64_t)p.sb_tiles * BNQ);
     f32x4 ss_cur = *(const f32x4*)(p.sb_stats + sb0 * 4), ss_next = ss_cur;
+    I8_DIAG(const unsigned long long dg_t1 = __builtin_amdgcn_s_memtime(); unsigned long long dg_ta = dg_t1;)
     for (int t = 0; t < n_tiles; ++t) {
         const int buf = t & 1;
         if (t + 1 < n_tiles) stage_issue(t + 1, buf ^ 1);
         if ((t % p.sb_tiles) == 0 && t + p.sb_tiles < n_tiles)
             ss_next = *(const f32x4*)(p.sb_stats + (sb0 + t / p.sb_tiles + 1) * 4);
+        I8_DIAG(const unsigned long long dg_tb = __builtin_amdgcn_s_memtime(); dg_bound += dg_tb - dg_ta;)
         if (buf == 0) tile_body(std::integral_constant<int, 0>{});
         else tile_body(std::integral_constant<int, 1>{});
+        I8_DIAG(unsigned long long dg_tc = __builtin_amdgcn_s_memtime(); dg_body += dg_tc - dg_tb;)
 
         if (((t + 1) % p.sb_tiles) == 0 || t + 1 == n_tiles) {
             // end of a superblock: combine the four row-groups' maxima of every user; row-group g then finishes its OW blocks
@@ -220,20 +262,26 @@ __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(Score
             const float scale = a_user * ss_cur[0];
             const float yh = TK ? ss_cur[1] : 0.f, dy = TK ? ss_cur[2] : 0.f, db = TK ? a_user * ss_cur[3] : 0.f;
             ss_cur = ss_next;
-            int m[NUB];
+            // a reduce-scatter in registers.  v_permlane32_swap exchanges the upper half of its first operand with the lower half
+            // of its second: max of the two results = (blocks j | j + NUB / 2) over the row-groups g and g ^ 2, in the (lower |
+            // upper) half of the wave.  v_permlane16_swap does the same with the odd and even rows of 16 lanes: (blocks k | k + OW)
+            // of the half's list over g and g ^ 1.  Row-group g = 2 (upper half) + (odd row) ends with the blocks OW g + o.
+            int h[NUB / 2], m[OW];
 #pragma unroll
-            for (int ub = 0; ub < NUB; ++ub) {
-                int x = bm[ub];
-                const int o1 = __shfl_xor(x, 16, 64);
-                x = x > o1 ? x : o1;
-                const int o2 = __shfl_xor(x, 32, 64);
-                m[ub] = x > o2 ? x : o2;
-                bm[ub] = INT_MIN;
+            for (int j = 0; j < NUB / 2; ++j) {
+                const auto r = __builtin_amdgcn_permlane32_swap((unsigned)bm[j], (unsigned)bm[j + NUB / 2], false, false);
+                h[j] = max((int)r[0], (int)r[1]);
             }
 #pragma unroll
             for (int o = 0; o < OW; ++o) {
-                const int mo = g == 0 ? m[o] : (g == 1 ? m[OW + o] : (g == 2 ? m[2 * OW + o] : m[3 * OW + o]));
-                float v = (float)mo * scale;                  // (exact below 2^24; beyond it one rounding, charged in i8_pair_err)
+                const auto r = __builtin_amdgcn_permlane16_swap((unsigned)h[o], (unsigned)h[o + OW], false, false);
+                m[o] = max((int)r[0], (int)r[1]);
+            }
+#pragma unroll
+            for (int ub = 0; ub < NUB; ++ub) bm[ub] = INT_MIN;
+#pragma unroll
+            for (int o = 0; o < OW; ++o) {
+                float v = (float)m[o] * scale;                // (exact below 2^24; beyond it one rounding, charged in i8_pair_err)
                 if (BIAS) v = v + own_bias[o];
                 if (own_u[o] < p.n_r) p.blockmax[sb * p.bm_stride + own_u[o]] = v;
                 if (TK) {
@@ -245,9 +293,11 @@ __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(Score
                     top[o][0] = fmaxf(top[o][0], lb);
                 }
             }
+            I8_DIAG(const unsigned long long dg_td = __builtin_amdgcn_s_memtime(); dg_sbend += dg_td - dg_tc; dg_tc = dg_td; ++dg_nsb;)
         }
         if (t + 1 < n_tiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        I8_DIAG(dg_ta = __builtin_amdgcn_s_memtime(); dg_bound += dg_ta - dg_tc;)
     }
     if (TK) {
 #pragma unroll
@@ -257,6 +307,13 @@ __global__ __launch_bounds__(NWQ * 64, 8 / NWQ) void blockmax_i8x16_kernel(Score
                 for (int j = 0; j < TK; ++j) p.chunk_top[((int64_t)chunk * TK + j) * p.bm_stride + own_u[o]] = top[o][j];
             }
     }
+#ifdef TREC_I8_DIAG
+    if (tid == 0 && blockIdx.x < (unsigned)I8_DIAG_WGS) {
+        unsigned long long* dg = g_i8_clk + (size_t)blockIdx.x * I8_DIAG_WORDS;
+        dg[0] = dg_t1 - dg_t0; dg[1] = dg_body; dg[2] = dg_bound; dg[3] = dg_sbend;
+        dg[4] = __builtin_amdgcn_s_memtime() - dg_t0; dg[5] = (unsigned long long)n_tiles | ((unsigned long long)dg_nsb << 32);
+    }
+#endif
 }
 
 template <int KT, bool BIAS, int TK, int NUB>
@@ -727,3 +784,13 @@ extern "C" int trec_score_gemm_blockmax_i8(const void* users_q, const void* item
     if (kpad == 128) return bias ? launch_i8x16_lists<128, true>(p, sb_rows, st) : launch_i8x16_lists<128, false>(p, sb_rows, st);
     return bias ? launch_i8x16_lists<64, true>(p, sb_rows, st) : launch_i8x16_lists<64, false>(p, sb_rows, st);
 }
+
+#ifdef TREC_I8_DIAG
+// diagnostics build only (not in include/tensorrec_hip.h): the clock sums of the last int8 stage launch, I8_DIAG_WORDS per workgroup
+extern "C" int trec_i8_diag_read(unsigned long long* out, long long n_words)
+{
+    if (n_words > (long long)I8_DIAG_WGS * I8_DIAG_WORDS) n_words = (long long)I8_DIAG_WGS * I8_DIAG_WORDS;
+    if (!out || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_i8_clk), sizeof(unsigned long long) * (size_t)n_words) != hipSuccess) return TREC_ERR_LAUNCH;
+    return TREC_OK;
+}
+#endif
